@@ -20,11 +20,20 @@ Weak scaling: per-GPU candidates are fixed; every rank fits the (replicated) GP 
 fit does not shard profitably -- and the only exchange is the RCCL
 all-gather of one (value, index) pair per rank.  `value` is the step time in ms (max over ranks).
 
-Also on the JSON line: `roofline` for the dominant kernel (the fp64 MFMA GEMM behind Cholesky
-SYRK/TRSM, posterior TRSM and TS SYRK) from per-launch HIP events recorded on the launch streams;
-`cpu_baseline`: the NumPy oracle (a port of the reference's CPU path) timed on this host's cores --
-the full n = 16384 fit and three full Thompson blocks; `parity_vs_oracle`: the device results of
-the same inputs against that oracle run; `configs`: BASELINE configs 2 and 5, untimed extras.
+A plain run sets up, warms up, times the steps and prints the one JSON line: `value` / `ms_per_step`,
+`result` (what the last timed step returned) and `roofline` for the dominant kernel (the fp64 MFMA GEMM
+behind Cholesky SYRK/TRSM, posterior TRSM and TS SYRK) from per-launch HIP events recorded on the
+launch streams of the timed steps.
+
+    --full               also everything measured beside the headline, untimed: the section timers of one
+                         extra step (the side targets inside `roofline`), `cpu_baseline` (the NumPy oracle,
+                         a port of the reference's CPU path, timed on this host's cores -- the full
+                         n = 16384 fit and three full Thompson blocks), `parity_vs_oracle` (the device results
+                         of the same inputs against that oracle run), `accuracy_vs_truth`, `conditioning` and
+                         `configs` (BASELINE configs 1, 2 and 5 and the other workloads of bench_extras.py);
+                         the full record goes out as a BENCH_DETAILS line before the JSON line
+    --dump-outputs DIR   after the timed steps, what the last one returned (lml, ts_best, ts_argmax) as
+                         float64 DIR/<name>.npy; the inputs are seeded, so two builds compare output for output
 """
 import argparse
 import json
@@ -555,6 +564,17 @@ def pmc_traffic(scaling):
   return None, None
 
 
+DUMP_KEYS = (('lml', 'lml'), ('ts_best', 'best'), ('ts_argmax', 'idx'))
+
+
+def dump_outputs(directory, result):
+  """ --dump-outputs: what the caller of the timed path received from its last step -- the fit's log marginal
+      likelihood, the best value of the Thompson draw and its global candidate index -- one float64 .npy each. """
+  os.makedirs(directory, exist_ok=True)
+  for name, key in DUMP_KEYS:
+    np.save(os.path.join(directory, name + '.npy'), np.array([result[key]], dtype=np.float64))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--gpus', type=int, default=1)
@@ -562,6 +582,11 @@ def main():
   # two by default: the ROCm runtime's one-off first-use work (code objects, queue resources: a 50 - 60 ms hole
   # in the first or second fit of a process, docs/NOTES_r03.md) should not land in the timed steps
   ap.add_argument('--warmup', type=int, default=2)
+  ap.add_argument('--full', action='store_true',
+                  help='also the untimed measurements beside the headline: section timers, CPU baseline, parity, '
+                       'accuracy, conditioning and the other configs (the --no-* options below trim them)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step returned as float64 DIR/<name>.npy')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--no-extras', action='store_true')
   ap.add_argument('--no-accuracy', action='store_true', help='skip the device / oracle vs extended-precision truth comparison (~5 s)')
@@ -600,12 +625,16 @@ def main():
   gstats = eng.gemm_profile(enable=False, fetch=True)
   elapsed = runner.max_over_ranks(elapsed)
   ms_per_step = elapsed * 1e3 / args.steps
-  # section breakdown from one extra, untimed step (section timers synchronise the host)
-  eng.timings(True)
-  runner.step()
-  runner.sync()
-  sections = eng.timings(False)
   result = dict(runner.result)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, result)
+  sections = {}
+  if args.full:
+    # section breakdown from one extra, untimed step (section timers synchronise the host)
+    eng.timings(True)
+    runner.step()
+    runner.sync()
+    sections = eng.timings(False)
 
   out = None
   if rank == 0:
@@ -680,7 +709,7 @@ def main():
       out[key + '_ms'] = round(sections[key], 4) if sections.get(key, 0) > 0 else None
     out['kernel_matrix_bytes_moved'] = KM_BYTES_MOVED
     out['kernel_matrix_bytes_section8d'] = KM_BYTES_8D
-    if not args.no_extras and world == 1:       # (ranks of a multi-process run stay in step: no rank-0-only extras)
+    if args.full and not args.no_extras and world == 1:       # (ranks of a multi-process run stay in step: no rank-0-only extras)
       # conditioning of the matrix that was factored (quoted next to the parity numbers):
       # lambda_max(K) by power iteration on the host, lambda_min(K + noise I) >= noise
       gp = eng.gp_fit(spec, prob['X'], prob['Y'] - prob['mean_c'], prob['noise'])
@@ -745,7 +774,7 @@ def main():
         except Exception as e:      # pylint: disable=broad-except
           out['configs']['C4_shards_on_1gpu'] = {'error': repr(e)}
       out['configs'].update(BX.run_all(eng, prob, spec, include_c4_full=not args.no_c4_full and args.scaling == 'weak'))
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
       out['cpu_baseline'], out['parity_vs_oracle'], c3 = cpu_baseline_and_parity(prob, runner.cands0, runner.U0, eng, spec, cpg)
       out.setdefault('configs', {})['C3_posterior'] = c3
       if not args.no_accuracy:
@@ -753,7 +782,12 @@ def main():
     elif not args.no_cpu_baseline:
       out['cpu_baseline'] = None
   runner.close()
-  if rank == 0:
+  if rank == 0 and not args.full:
+    # a plain run: the contract's line alone (no BENCH_DETAILS record before it)
+    contract = contract_line(out)
+    contract.pop('details')
+    print(json.dumps(contract), flush=True)
+  elif rank == 0:
     sys.stdout.flush()
     # Everything measured goes out on a line of its own that is NOT a JSON line ('BENCH_DETAILS ' in front; also
     # written to gpurun_out/bench_details.json when that directory exists); the ONE JSON line, last thing on stdout,

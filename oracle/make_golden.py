@@ -830,9 +830,45 @@ def gen_engine_traces():
   print('engine traces: %d scenarios, %d calls' % (len(scenarios), total))
 
 
+CPU_LEGS_CASES = ((384, 128), (2048, 1100))
+
+
+def cpu_legs_inputs(n, m):
+  """ The inputs of tests/test_bench_helpers.py::test_cpu_legs_agree_stage_by_stage: config 3's first n points, m
+      seed-0 candidates, seed-1 normals. """
+  import bench_configs as BC
+  prob = BC.config3()
+  cands = np.random.RandomState(0).rand(m, BC.DIM)
+  U = np.random.RandomState(1).randn(m)
+  return prob, prob['X'][:n], prob['Y'][:n], cands, U
+
+
+def gen_cpu_legs_cases():
+  """ bench.py's CPU leg on the reference's OWN functions (SEKernel, stable_cholesky, solve_*_triangular), stage by stage
+      (bench.oracle_stages), at the sizes of test_cpu_legs_agree_stage_by_stage -> tests/golden/cpu_legs_reference.npz:
+      what the oracle's port must reproduce where no Dragonfly checkout is present. """
+  import bench
+  os.environ['DRAGONFLY_REFERENCE'] = REF
+  out = {}
+  for n, m in CPU_LEGS_CASES:
+    prob, X, Y, cands, U = cpu_legs_inputs(n, m)
+    fr, kr, kind, _ = bench.cpu_functions(prob)
+    assert kind == 'reference'
+    _, a = bench.oracle_stages(fr, kr, X, Y, prob['mean_c'], prob['noise'], [cands], [U], posterior_chunks=[cands])
+    blk = a['blocks'][0]
+    out.update({'n%d_alpha' % n: a['alpha'], 'n%d_lml' % n: np.float64(a['lml']), 'n%d_mu' % n: blk['mu'],
+                'n%d_sd' % n: blk['sd'], 'n%d_draw' % n: blk['draw'], 'n%d_argmax' % n: np.int64(blk['argmax']),
+                'n%d_posterior_sd' % n: a['posterior'][0]['sd']})
+  np.savez(os.path.join(OUT, 'cpu_legs_reference.npz'), **out)
+  print('wrote cpu_legs_reference: %s' % sorted(out))
+
+
 if __name__ == '__main__':
   os.makedirs(OUT, exist_ok=True)
   import_reference()
+  if len(sys.argv) > 1 and sys.argv[1] == 'cpu_legs':
+    gen_cpu_legs_cases()
+    sys.exit(0)
   if len(sys.argv) > 1 and sys.argv[1] == 'mfgp':
     gen_mfgp_case()
     sys.exit(0)

@@ -1,13 +1,14 @@
 """CPU: the measurement code's own arithmetic (bench.py) -- the error norms it reports, the fp64-pipe bound, and the
-two CPU legs (the oracle's port and, where a Dragonfly checkout exists, the reference's own functions) agreeing
-bit for bit stage by stage."""
+two CPU legs stage by stage: the oracle's port against the reference's stored outputs and, where a Dragonfly checkout
+exists, against the reference's own functions bit for bit."""
 import os
 
 import numpy as np
 import pytest
 
 import bench
-import bench_configs as BC
+from conftest import load_golden, relerr
+from oracle import make_golden as MG
 
 
 def test_error_norms():
@@ -31,22 +32,29 @@ def test_fp64_pipe_bound():
 # (n = 2048 with 1100 candidates: OpenBLAS / LAPACK take their blocked, multi-threaded code paths there -- dpotrf's
 #  recursive panels, dtrsm / dgemm blocking -- which n = 384 does not reach: `kind: port` is pinned to the reference's
 #  own functions at a size where the library's blocking matters)
-@pytest.mark.parametrize('n,m', [(384, 128), (2048, 1100)])
+#  Without a Dragonfly checkout the port is held to the reference's outputs stored by `python oracle/make_golden.py cpu_legs`
+#  (tests/golden/cpu_legs_reference.npz): to 1e-12, as BLAS results move in the last bits with the host's thread count;
+#  with a checkout, the two legs are also run side by side and must agree bit for bit.
+@pytest.mark.parametrize('n,m', MG.CPU_LEGS_CASES)
 def test_cpu_legs_agree_stage_by_stage(monkeypatch, n, m):
-  ref = os.environ.get('DRAGONFLY_REFERENCE', '/root/reference')
-  if not os.path.isdir(os.path.join(ref, 'dragonfly')):
-    pytest.skip('needs the reference tree (build container only)')
-  prob = BC.config3()
-  X, Y = prob['X'][:n], prob['Y'][:n]
-  cands = np.random.RandomState(0).rand(m, BC.DIM)
-  U = np.random.RandomState(1).randn(m)
-  monkeypatch.setenv('DRAGONFLY_REFERENCE', ref)
-  fr, kr, kind_r, _ = bench.cpu_functions(prob)
+  prob, X, Y, cands, U = MG.cpu_legs_inputs(n, m)
   monkeypatch.setenv('DRAGONFLY_REFERENCE', '')
   fp, kp, kind_p, _ = bench.cpu_functions(prob)
-  assert (kind_r, kind_p) == ('reference', 'port')
-  _, a = bench.oracle_stages(fr, kr, X, Y, prob['mean_c'], prob['noise'], [cands], [U], posterior_chunks=[cands])
+  assert kind_p == 'port'
   _, b = bench.oracle_stages(fp, kp, X, Y, prob['mean_c'], prob['noise'], [cands], [U], posterior_chunks=[cands])
+  g = load_golden('cpu_legs_reference')
+  want = lambda k: g['n%d_%s' % (n, k)]
+  assert relerr(b['alpha'], want('alpha')) < 1e-12 and abs(b['lml'] - float(want('lml'))) < 1e-12 * abs(float(want('lml')))
+  for k in ('mu', 'sd', 'draw'):
+    assert relerr(b['blocks'][0][k], want(k)) < 1e-12, k
+  assert b['blocks'][0]['argmax'] == int(want('argmax'))
+  assert relerr(b['posterior'][0]['sd'], want('posterior_sd')) < 1e-12
+  if not os.path.isdir(os.path.join(MG.REF, 'dragonfly')):
+    return
+  monkeypatch.setenv('DRAGONFLY_REFERENCE', MG.REF)
+  fr, kr, kind_r, _ = bench.cpu_functions(prob)
+  assert kind_r == 'reference'
+  _, a = bench.oracle_stages(fr, kr, X, Y, prob['mean_c'], prob['noise'], [cands], [U], posterior_chunks=[cands])
   assert np.array_equal(a['alpha'], b['alpha']) and a['lml'] == b['lml']
   for key in ('mu', 'sd', 'draw'):
     assert np.array_equal(a['blocks'][0][key], b['blocks'][0][key])
@@ -77,3 +85,13 @@ def test_contract_line_carries_the_side_targets_inside_roofline():
   assert r['C2_chol_ms'] == full['configs']['C2']['sections_ms']['chol']
   assert set(line['cpu_baseline']) == {'value', 'unit', 'cores', 'kind', 'sample'}
   assert 'workload' in line['config'] and 'model' not in line['config']
+
+
+def test_dump_outputs_writes_the_last_step_as_float64(tmp_path):
+  """ --dump-outputs: one float64 .npy per value the timed path returns; an index survives the cast exactly. """
+  result = {'lml': -8983.546226064143, 'best': 10.538616786596952, 'idx': 2097151}
+  bench.dump_outputs(str(tmp_path / 'out'), result)
+  assert sorted(os.listdir(str(tmp_path / 'out'))) == ['lml.npy', 'ts_argmax.npy', 'ts_best.npy']
+  for name, key in bench.DUMP_KEYS:
+    a = np.load(str(tmp_path / 'out' / (name + '.npy')))
+    assert a.dtype == np.float64 and a.shape == (1,) and a[0] == result[key]
