@@ -1655,7 +1655,7 @@ extern "C" int dfh_gp_add_ucb_group(dfh_gp* gp, int32_t group, double beta, cons
                                     double* vals_out, double* best_val, int64_t* best_idx) {
   DFH_ARG(gp && Xg && m >= 1);
   DFH_ARG(!gp->gram);      // needs the kernel: this posterior was built from a Gram matrix
-  DFH_ARG(gp->kd.multi && !gp->kd.product && group >= 0 && group < gp->kd.n_parts);   // additive kernels only
+  DFH_ARG(gp->kd.multi && !gp->kd.product && !gp->kd.esp && group >= 0 && group < gp->kd.n_parts);   // additive kernels only
   const PartDev& pd = gp->kd.parts[group];
   int gdim = 0;
   for (int c = 0; c < pd.kc; ++c) gdim += gp->kd.cols[pd.poff + c] >= 0;
@@ -1674,7 +1674,7 @@ extern "C" int dfh_gp_add_ucb_all(dfh_gp* gp, const double* betas, const double*
                                   double* vals_out, double* best_vals, int64_t* best_idx) {
   DFH_ARG(gp && betas && Xg_all && m_per_group && best_vals && best_idx);
   DFH_ARG(!gp->gram);
-  DFH_ARG(gp->kd.multi && !gp->kd.product);
+  DFH_ARG(gp->kd.multi && !gp->kd.product && !gp->kd.esp);     // additive kernels only
   dfh_ctx* ctx = gp->ctx;
   DFH_HIP(hipSetDevice(ctx->device));
   const KernDev& kd = gp->kd;

@@ -2830,7 +2830,7 @@ bool lml_wg_fused_applies(const KernDev* kds, int count, int64_t n) {
   static const int max_n = std::min(255, env_int("DFH_LML_FUSED_MAX_N", (int)LMLF_MAX_N));
   if (count < 1 || count > fused_max || n < 1 || n > max_n) return false;
   for (int c = 0; c < count; ++c)
-    if (kds[c].P > TINY_MAX_P || kds[c].n_parts > TINY_MAX_PARTS || kds[c].P < 1 || !kds[c].stationary ||
+    if (kds[c].P > TINY_MAX_P || kds[c].n_parts > TINY_MAX_PARTS || kds[c].P < 1 || !kds[c].stationary || kds[c].esp ||
         n * (int64_t)(kds[c].P + kds[c].n_parts) > LMLF_LDS_DOUBLES) return false;
   return true;
 }

@@ -262,7 +262,14 @@ struct KernDev {
   void* d_blob = nullptr;      // the one device allocation behind the four pointers (owned if set)
   double kxx = 0.0;            // prior variance k(x,x) of a stationary kernel
   bool stationary = true;      // false with a Poly / ExpDecay part: k(x,x) depends on x (prior_diag)
+  // ESP kernel (DFH_KERNEL_ESP): one SE / Matern part per column, combined by Newton-Girard into the
+  // elementary symmetric polynomial of order esp_order, times outer_scale.  multi is set (several parts)
+  // and product is not: every consumer of multi / product must test esp first.
+  bool esp = false;
+  int esp_order = 0;
 };
+constexpr int ESP_MAX_ORDER = 32;      // register bucket of the ESP kernel-matrix kernel (kernmat.hip)
+constexpr int ESP_MAX_DIM = 256;       // one tile's columns of both operands in LDS
 int kerndev_build(dfh_ctx* ctx, const dfh_kernel_desc* k, KernDev* out);
 // host-only part of kerndev_build, and the upload of several descriptors with one copy into a
 // caller-provided device blob (kerndev_blob_bytes each, in order); such KernDevs own no memory
@@ -304,6 +311,7 @@ int kerndev_clone(dfh_ctx* ctx, const KernDev& src, KernDev* out);   // deep cop
 void kerndev_free(KernDev* kd);
 double kerndev_part_kxx(const KernDev& kd, int part);
 // out[i] = k(x_i, x_i) from the packed inputs of m points (any kernel; needed when !kd.stationary)
+// (an ESP kernel: kd.kxx for every point; the posterior paths use kd.kxx directly for every stationary kernel)
 // part_lo / part_hi (default: all parts): the prior variance of those groups of an additive kernel only
 int prior_diag(dfh_ctx* ctx, const KernDev& kd, const double* Xp, const double* Np, int64_t m, double* out, int part_lo = 0,
                int part_hi = -1);

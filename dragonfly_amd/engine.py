@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ACQ_EI, ACQ_MEAN, ACQ_PI, ACQ_STD, ACQ_TTEI, ACQ_UCB, GET_ALPHA, GET_K, GET_L,
-                   INT32_MIN, KERNEL_ADDITIVE, KERNEL_EXPDECAY, KERNEL_MATERN, KERNEL_POLY, KERNEL_PRODUCT, KERNEL_SE,
+                   INT32_MIN, KERNEL_ADDITIVE, KERNEL_ESP, KERNEL_EXPDECAY, KERNEL_MATERN, KERNEL_POLY, KERNEL_PRODUCT, KERNEL_SE,
                    KernelDesc,
                    check)
 
@@ -142,7 +142,10 @@ class KernelSpec(object):
       its factors may be any of the four single kinds, an additive kernel's se / matern / poly).
       A product may hold ADDITIVE FACTORS (an AdditiveKernel among its kernels): list the factor's
       groups like any others and give group_factors[g] = index of the factor group g belongs to
-      (non-decreasing), factor_sums[f] = True for an additive factor, factor_scales[f] = its scale. """
+      (non-decreasing), factor_sums[f] = True for an additive factor, factor_scales[f] = its scale.
+      'esp' (ESPKernel, kernel.py:671-744): nu = order, one 1-D se / matern kernel per column in
+      column order (sub_kinds / sub_scales / sub_nus / sub_bandwidths, one entry each; groups
+      default to [[0], [1], ..]). """
 
   def __init__(self, kind, dim, scale, bandwidths=None, nu=0.0, groups=None, sub_kinds=None,
                sub_scales=None, sub_nus=None, sub_bandwidths=None, group_factors=None, factor_sums=None,
@@ -158,6 +161,8 @@ class KernelSpec(object):
     self.sub_nus = sub_nus
     self.sub_bandwidths = sub_bandwidths
     self.group_factors, self.factor_sums, self.factor_scales = group_factors, factor_sums, factor_scales
+    if kind == 'esp' and groups is None:
+      self.groups = [[c] for c in range(self.dim)]
     self._keep = []
 
   def signature(self):
@@ -189,10 +194,11 @@ class KernelSpec(object):
       self._keep.append(bw)
       d.bw = bw.ctypes.data_as(_lib.c_double_p)
       d.n_groups = 0
-    elif self.kind in ('additive', 'product'):
-      d.kind = KERNEL_ADDITIVE if self.kind == 'additive' else KERNEL_PRODUCT
+    elif self.kind in ('additive', 'product', 'esp'):
+      d.kind = {'additive': KERNEL_ADDITIVE, 'product': KERNEL_PRODUCT, 'esp': KERNEL_ESP}[self.kind]
       d.dim = self.dim
       d.scale = self.scale
+      d.nu = self.nu if self.kind == 'esp' else 0.0     # ESP: the order
       ng = len(self.groups)
       off = np.zeros(ng + 1, dtype=np.int32)
       off[1:] = np.cumsum([len(g) for g in self.groups])

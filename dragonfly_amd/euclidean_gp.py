@@ -24,7 +24,7 @@ from .kernel import _as_2d_array
 from .doo import pdoo_maximise_batched
 from .oper_utils import random_maximise, random_sample_cts_dscr
 from .hp_sampling import PosteriorHPSampler
-from .hp_layout import consume_kernel_hps, describe_kernel_hps, group_kernel_args
+from .hp_layout import consume_kernel_hps, describe_kernel_hps, group_kernel_args, layout_key
 from .option_handler import get_option_specs, load_options
 
 _DFLT_KERNEL_TYPE = 'matern'
@@ -60,7 +60,12 @@ add_gp_args = [
   get_option_specs('num_groups_per_group_size', False, -1, ''),
   get_option_specs('add_group_size_criterion', False, 'sampled', ''),
 ]
-euclidean_gp_args = mandatory_gp_args + basic_euc_gp_args + matern_gp_args + add_gp_args
+esp_gp_args = [
+  get_option_specs('esp_order', False, -1, 'Order of the esp kernel. '),
+  get_option_specs('esp_kernel_type', False, 'se', 'Specify type of kernel. This depends on the application.'),
+  get_option_specs('esp_matern_nu', False, -1.0, 'Specify the nu value for matern kernel. If negative, will fit.'),
+]
+euclidean_gp_args = mandatory_gp_args + basic_euc_gp_args + matern_gp_args + add_gp_args + esp_gp_args
 
 
 class EuclideanGP(GP):
@@ -76,12 +81,14 @@ class EuclideanGP(GP):
   @classmethod
   def _get_kernel_from_type(cls, kernel_type, kernel_hyperparams):
     """ A kernel given by name and a dictionary of its parameters (euclidean_gp.py:154-175); the
-        two Euclidean kernels that run on the device. """
+        Euclidean kernels that run on the device. """
     hp = kernel_hyperparams
     if kernel_type == 'se':
       return gp_kernel.SEKernel(hp['dim'], hp['scale'], hp['dim_bandwidths'])
     if kernel_type == 'matern':
       return gp_kernel.MaternKernel(hp['dim'], hp['nu'], hp['scale'], hp['dim_bandwidths'])
+    if kernel_type == 'esp':
+      return gp_kernel.ESPKernelSE(hp['dim'], hp['scale'], hp['order'], hp['dim_bandwidths'])
     raise ValueError('Cannot construct kernel from kernel_type %s.' % (kernel_type))
 
   def _child_str(self):
@@ -120,6 +127,11 @@ def prep_euclidean_integral_kernel_hyperparams(kernel_type, gp_fitter_options, d
   hyperparams['dim'] = domain_dim
   if kernel_type == 'matern' and gp_fitter_options.matern_nu > 0:
     hyperparams['nu'] = gp_fitter_options.matern_nu
+  elif kernel_type == 'esp':
+    if gp_fitter_options.esp_order > 0:
+      hyperparams['esp_order'] = gp_fitter_options.esp_order
+    if gp_fitter_options.esp_matern_nu > 0:
+      hyperparams['esp_matern_nu'] = gp_fitter_options.esp_matern_nu
   return hyperparams
 
 
@@ -139,13 +151,27 @@ def get_euclidean_integral_gp_kernel_with_scale(kernel_type, scale, kernel_hyper
                                                 use_same_bandwidth, add_gp_groupings=None,
                                                 esp_kernel_type=None):
   """ The kernel a hyper-parameter vector describes (interface of euclidean_gp.py:808-900 for the
-      se / matern / poly / expdecay kernels, plain or additive; the reference's 'esp' kernels are not
-      part of the device path).  Which values of the two vectors feed which argument of which kernel
-      class is the table of dragonfly_amd/hp_layout.py.  An additive kernel carries the scale itself
-      and its groups' kernels scale 1 (kernel.py:484-494).  Returns (kernel, left-over continuous,
-      left-over discrete hyper-parameters). """
-  # pylint: disable=unused-argument
+      se / matern / poly / expdecay kernels, plain or additive, and the esp kernels).  Which values of
+      the two vectors feed which argument of which kernel class is the table of
+      dragonfly_amd/hp_layout.py.  An additive kernel carries the scale itself and its groups'
+      kernels scale 1 (kernel.py:484-494).  An ESP kernel ignores add_gp_groupings; its order comes
+      off the end of the discrete vector, its nu (a list, one per dimension) off the front
+      (:815-820, 845-851, 882-891).  Returns (kernel, left-over continuous, left-over discrete
+      hyper-parameters). """
   dim = kernel_hyperparams['dim']
+  if kernel_type == 'esp':
+    if esp_kernel_type not in ('se', 'matern'):
+      raise Exception('Unknown esp_kernel_type %s!' % (esp_kernel_type))
+    values, _, gp_cts_hps, gp_dscr_hps = consume_kernel_hps(layout_key(kernel_type, esp_kernel_type), dim,
+                                                            kernel_hyperparams, gp_cts_hps, gp_dscr_hps,
+                                                            use_same_bandwidth)
+    order = int(np.asarray(values['order']).item())
+    if esp_kernel_type == 'se':
+      kernel = gp_kernel.ESPKernelSE(dim=dim, scale=scale, order=order, dim_bandwidths=values['dim_bandwidths'])
+    else:
+      kernel = gp_kernel.ESPKernelMatern(dim=dim, nu=[values['nu']] * dim, scale=scale, order=order,
+                                         dim_bandwidths=values['dim_bandwidths'])
+    return kernel, gp_cts_hps, gp_dscr_hps
   values, cls_name, gp_cts_hps, gp_dscr_hps = consume_kernel_hps(kernel_type, dim, kernel_hyperparams,
                                                                  gp_cts_hps, gp_dscr_hps, use_same_bandwidth)
   additive = add_gp_groupings is not None
@@ -285,9 +311,8 @@ class EuclideanGPFitter(object):
       raise ValueError('Unknown kernel_type. Should be either se, matern or poly.')
     if self.options.kernel_type == 'poly':
       raise NotImplementedError('Not implemented Poly kernel yet.')       # euclidean_gp.py:280-282: nor has the reference
-    if self.options.kernel_type == 'esp':
-      raise NotImplementedError('esp kernels are outside the device path (SURVEY.md section 2); '
-                                'use the reference fitter for them.')
+    if self.options.kernel_type == 'esp' and self.options.esp_kernel_type not in ['se', 'matern']:
+      raise NotImplementedError('Not implemented yet.')                  # euclidean_gp.py:285-286
     if self.options.noise_var_type not in ['tune', 'label', 'value']:
       raise ValueError('Unknown noise_var_type. Should be either tune, label or value.')
     if self.options.mean_func_type not in ['mean', 'median', 'const', 'zero', 'tune']:
@@ -302,11 +327,13 @@ class EuclideanGPFitter(object):
     X_std_norm = np.linalg.norm(_as_2d_array(self.X), 'fro') + 1e-4
     single_bandwidth_log_bounds = [np.log(0.01 * X_std_norm), np.log(10 * X_std_norm)]
     boxes = {'dim_bandwidths': single_bandwidth_log_bounds, 'same_dim_bandwidths': single_bandwidth_log_bounds}
-    value_lists = {'nu': [0.5, 1.5, 2.5]}
+    # (an ESP kernel has a bandwidth box per dimension whatever use_same_bandwidth says, and a discrete
+    # order over 1..dim last when it is tuned: euclidean_gp.py:249-251, 283-300)
+    value_lists = {'nu': [0.5, 1.5, 2.5], 'esp_order': list(range(1, max(self.dim, self.options.esp_order) + 1))}
     kernel_hyperparams = prep_euclidean_integral_kernel_hyperparams(self.kernel_type, self.options, self.dim)
     self.bandwidth_log_bounds = []
-    for name, source, count in describe_kernel_hps(self.kernel_type, self.dim, kernel_hyperparams,
-                                                   self.options.use_same_bandwidth):
+    for name, source, count in describe_kernel_hps(layout_key(self.kernel_type, self.options.esp_kernel_type),
+                                                   self.dim, kernel_hyperparams, self.options.use_same_bandwidth):
       if source == 'cts':
         self.bandwidth_log_bounds += [boxes[name]] * count
         self.param_order += [[name, "cts"] for _ in range(count)]
@@ -314,7 +341,7 @@ class EuclideanGPFitter(object):
         self.dscr_hp_vals.append(value_lists[name])
         self.param_order.append([name, "dscr"])
     self.cts_hp_bounds += [self.scale_log_bounds] + self.bandwidth_log_bounds
-    if self.options.use_additive_gp:
+    if self._add_model():
       self.add_group_size_idx_in_dscr_hp_vals = len(self.dscr_hp_vals)
       self.add_max_group_size = min(self.options.add_max_group_size, self.dim)
       self.dscr_hp_vals.append([x+1 for x in range(self.add_max_group_size)])
@@ -364,7 +391,15 @@ class EuclideanGPFitter(object):
     self.hp_sampler = _rand_exp_sampling_wrap
 
   def _uses_additive_model(self):
-    return self.options.use_additive_gp
+    return self._add_model()
+
+  def _add_model(self):
+    """ use_additive_gp, which an ESP kernel ignores -- in every path here.  The reference ignores it only in the
+        set-up (euclidean_gp.py:244); its optimiser, sampler and _child_build_gp (:329-332) then treat the ESP
+        fitter as additive, strip a group size that was never added and read groupings that were never drawn, so
+        that kernel_type='esp' with use_additive_gp=True fails there (IndexError) while this fitter fits the plain
+        ESP kernel the set-up describes. """
+    return self.options.use_additive_gp and getattr(self, 'kernel_type', None) != 'esp'
 
   # -- building GPs (gp_core.py:501-543; euclidean_gp.py:325-339) ----------------------------------
   def _device_X(self):
@@ -420,12 +455,12 @@ class EuclideanGPFitter(object):
     kernel_hyperparams = prep_euclidean_integral_kernel_hyperparams(self.kernel_type,
                                                                     self.options, self.dim)
     add_gp_groupings = None
-    if self.options.use_additive_gp:
+    if self._add_model():
       gp_dscr_hps = gp_dscr_hps[:-1]
       add_gp_groupings = other_gp_params.add_gp_groupings
     return get_euclidean_integral_gp_kernel(self.kernel_type, kernel_hyperparams, gp_cts_hps,
                                             gp_dscr_hps, self.options.use_same_bandwidth,
-                                            add_gp_groupings)
+                                            add_gp_groupings, self.options.esp_kernel_type)
 
   def _child_build_gp(self, mean_func, noise_var, gp_cts_hps, gp_dscr_hps,
                       other_gp_params=None, *args, **kwargs):
@@ -482,7 +517,7 @@ class EuclideanGPFitter(object):
 
   def _optimise_cts_hps_for_given_dscr_hps(self, given_dscr_hps):
     """ gp_core.py:576-583 / euclidean_gp.py:303-313 """
-    if self.options.use_additive_gp:
+    if self._add_model():
       return optimise_cts_hps_for_given_dscr_hps_in_add_model(list(given_dscr_hps), \
         self.options.num_groups_per_group_size, self.dim, self.hp_tune_max_evals, \
         self.cts_hp_optimise, self._tuning_objective_batch)
@@ -497,7 +532,7 @@ class EuclideanGPFitter(object):
 
   def _sample_cts_dscr_hps_for_post_sampling(self, num_samples):
     """ gp_core.py:592-726 """
-    additive = self.options.use_additive_gp
+    additive = self._add_model()
     sampler = PosteriorHPSampler(self, add_dim=self.dim if additive else None,
                                  add_max_group_size=self.add_max_group_size if additive else None)
     return sampler.sample(num_samples)

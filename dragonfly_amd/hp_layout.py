@@ -13,7 +13,13 @@ fields a kernel consumes, each with
                        them (use_same_bandwidth); a group of an additive kernel takes its own
                        coordinates' values,
             'scalar'   one value,
-            'vector'   one value per input dimension, handed to every group whole.
+            'vector'   one value per input dimension, handed to every group whole,
+            'esp'      the ESP kernel's bandwidths (euclidean_gp.py:845-851): values [0:dim] when the fitter
+                       ties them, [0:dim*dim] -- whatever is left -- when it does not; the fitter has a box
+                       per dimension either way (:283-300).
+    A 'dscr_last' source is one value off the END of the discrete vector: the ESP order (:815-820).
+
+The ESP kernel (kernel_type 'esp') is keyed by its member kernel: 'esp_se' / 'esp_matern'.
 
 `consume_kernel_hps` (building kernels: the factory below it, both fitters) and `describe_kernel_hps`
 (sizing the hyper-parameter boxes and the `param_order` bookkeeping the posterior sampler walks)
@@ -33,7 +39,19 @@ KERNEL_HP_LAYOUT = {
                           HPField('order', 'dscr', 'scalar', 'order', 'order')]),
   'expdecay': ('ExpDecayKernel', [HPField('offset', 'cts', 'scalar', None, 'expdecay_offset'),
                                   HPField('powers', 'cts', 'vector', None, 'expdecay_powers')]),
+  'esp_se': ('ESPKernelSE', [HPField('dim_bandwidths', 'cts', 'esp', None, 'dim_bandwidths'),
+                             HPField('order', 'dscr_last', 'scalar', 'esp_order', 'esp_order')]),
+  'esp_matern': ('ESPKernelMatern', [HPField('dim_bandwidths', 'cts', 'esp', None, 'dim_bandwidths'),
+                                     HPField('nu', 'dscr', 'scalar', 'esp_matern_nu', 'nu'),
+                                     HPField('order', 'dscr_last', 'scalar', 'esp_order', 'esp_order')]),
 }
+
+
+def layout_key(kernel_type, esp_kernel_type=None):
+  """ the table's key: the kernel type, or for 'esp' its member kernel """
+  if kernel_type == 'esp':
+    return 'esp_%s' % (esp_kernel_type)
+  return kernel_type
 
 
 def _is_pinned(field, kernel_hyperparams):
@@ -52,7 +70,11 @@ def consume_kernel_hps(kernel_type, dim, kernel_hyperparams, cts_hps, dscr_hps, 
   values = {}
   for field in fields:
     if field.source == 'cts':
-      if field.shape == 'per_dim' and tied:
+      if field.shape == 'esp':
+        span = dim if tied else dim * dim
+        values[field.arg] = np.exp(cts_hps[0:span])
+        cts_hps = cts_hps[span:]
+      elif field.shape == 'per_dim' and tied:
         values[field.arg] = [np.exp(cts_hps[0])] * dim
         cts_hps = cts_hps[1:]
       elif field.shape == 'scalar':
@@ -63,6 +85,9 @@ def consume_kernel_hps(kernel_type, dim, kernel_hyperparams, cts_hps, dscr_hps, 
         cts_hps = cts_hps[dim:]
     elif _is_pinned(field, kernel_hyperparams):
       values[field.arg] = kernel_hyperparams[field.pinned_by]
+    elif field.source == 'dscr_last':
+      values[field.arg] = dscr_hps[-1]
+      dscr_hps = dscr_hps[:-1]
     else:
       values[field.arg] = dscr_hps[0]
       dscr_hps = dscr_hps[1:]
@@ -85,9 +110,11 @@ def describe_kernel_hps(kernel_type, dim, kernel_hyperparams, tied):
   _, fields = KERNEL_HP_LAYOUT[kernel_type]
   out = []
   for field in fields:
-    if field.source == 'dscr':
+    if field.source in ('dscr', 'dscr_last'):
       if not _is_pinned(field, kernel_hyperparams):
         out.append((field.param_name, 'dscr', 1))
+    elif field.shape == 'esp':
+      out.append((field.param_name, 'cts', dim))
     elif field.shape == 'per_dim' and tied:
       out.append(('same_' + field.param_name, 'cts', 1))
     elif field.shape == 'scalar':

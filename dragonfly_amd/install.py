@@ -7,9 +7,11 @@
 
 What is rebound (each is a *name looked up at call time* in the reference, so no reference file is
 edited):
-  S1 kernels   dragonfly.gp.kernel.SEKernel / MaternKernel / AdditiveKernel  -> dragonfly_amd.kernel
+  S1 kernels   dragonfly.gp.kernel.SEKernel / MaternKernel / AdditiveKernel / ESPKernelSE /
+               ESPKernelMatern -> dragonfly_amd.kernel
                (the Euclidean kernel factory resolves `gp_kernel.SEKernel` etc. at call time:
-               dragonfly/gp/euclidean_gp.py:17,850,859,896)
+               dragonfly/gp/euclidean_gp.py:17,850,859,882,890,896); an ESP kernel then is one
+               kernel-matrix launch instead of one per dimension and a host recursion
   S2/S3 GP     dragonfly.gp.euclidean_gp.EuclideanGP -> dragonfly_amd.euclidean_gp.EuclideanGP
                (every Euclidean fitter constructs its GP through this module global,
                dragonfly/gp/euclidean_gp.py:338)
@@ -73,7 +75,7 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False):
     _saved.append((mod, name, getattr(mod, name)))
     setattr(mod, name, new)
     patched.append('%s.%s' % (mod.__name__, name))
-  for name in ('SEKernel', 'MaternKernel', 'AdditiveKernel'):
+  for name in ('SEKernel', 'MaternKernel', 'AdditiveKernel', 'ESPKernelSE', 'ESPKernelMatern'):
     _set(ref_kernel, name, getattr(kernel, name))
   _set(ref_egp, 'EuclideanGP', euclidean_gp.EuclideanGP)
 

@@ -1,5 +1,5 @@
-"""Euclidean kernels evaluated on the MI355X: SE, Matern, Polynomial, Exponential-decay, Additive
-and coordinate-wise Product.
+"""Euclidean kernels evaluated on the MI355X: SE, Matern, Polynomial, Exponential-decay, Additive,
+coordinate-wise Product and ESP (elementary symmetric polynomial of 1-D kernels).
 
 Host-side counterpart of dragonfly/gp/kernel.py: the class names, constructor arguments, the
 `hyperparams` dictionary, the printed form and the error behaviour are the reference's (its lines
@@ -467,3 +467,107 @@ class CoordinateProductKernel(_GroupedKernel):
     for kern, coords in zip(self.kernel_list, self.coordinate_list):
       K *= kern(X1[:, coords], X2[:, coords])
     return K
+
+
+# Orders above this stay in host-kernel mode: the device keeps the power sums in registers (csrc/kernmat.hip), and at
+# such orders the reference's Newton-Girard recursion is dominated by cancellation in fp64 anyway.
+ESP_DEVICE_MAX_ORDER = 32
+ESP_DEVICE_MAX_DIM = 256
+
+
+class ESPKernel(_EuclideanDeviceKernel):
+  """ The ESP kernel of Kandasamy & Yu (2016), 'Additive Approximations in High Dimensional
+      Nonparametric Regression' (kernel.py:671-726): scale * e_order(k_0(x_0, y_0), .., k_{d-1}(x_{d-1},
+      y_{d-1})), kernel_list[i] a 1-D kernel of column i.  The bandwidths live in kernel_list, `hyperparams`
+      holds scale and order only. """
+
+  def __init__(self, scale, order, kernel_list):
+    super(ESPKernel, self).__init__()
+    self.dim = len(kernel_list)
+    self.kernel_list = kernel_list
+    self.add_hyperparams(scale=scale, order=order)
+    if self.dim < 0:
+      raise ValueError("dim cannot not be negative")
+    if order > self.dim:
+      raise ValueError("order must be less than or equal to dim")
+    if order < 1:
+      raise ValueError("order must be an integer between 1 and dim")
+
+  def is_guaranteed_psd(self):
+    return all([kern.is_guaranteed_psd() for kern in self.kernel_list])
+
+  def get_scaled_repr(self, X):
+    raise NotImplementedError('Not defined for the ESP kernel.')
+
+  def _members(self):
+    """ (kind, scale, nu, bandwidth) of every column's kernel, or None if one is not a 1-D SE / Matern """
+    out = []
+    for kern in self.kernel_list:
+      kind = _factor_kind(kern)
+      if kind not in ('se', 'matern') or getattr(kern, 'dim', None) != 1:
+        return None
+      scale, nu, bws = _factor_fields(kern, kind)
+      if bws.size != 1:
+        return None
+      out.append((kind, scale, nu, float(bws[0])))
+    return out
+
+  def has_device_spec(self):
+    order = self.hyperparams['order']
+    return float(order) == int(order) and 1 <= int(order) <= min(ESP_DEVICE_MAX_ORDER, self.dim) and \
+           self.dim <= ESP_DEVICE_MAX_DIM and self._members() is not None
+
+  def to_spec(self, in_dim=None):
+    if not self.has_device_spec():
+      raise TypeError('This ESP kernel does not run on the device (1-D SE / Matern members, order <= %d, '
+                      'dim <= %d).' % (ESP_DEVICE_MAX_ORDER, ESP_DEVICE_MAX_DIM))
+    if in_dim is not None and in_dim != self.dim:
+      raise ValueError('Second dimension of X1 and X2 should be %d (one column per kernel).' % (self.dim))
+    members = self._members()
+    return KernelSpec('esp', self.dim, self.hyperparams['scale'], nu=int(self.hyperparams['order']),
+                      sub_kinds=[m[0] for m in members], sub_scales=[m[1] for m in members],
+                      sub_nus=[m[2] for m in members], sub_bandwidths=[[m[3]] for m in members])
+
+  def _host_compose(self, X1, X2):
+    """ kernel.py:693-726, the reference's formula with each column's kernel evaluated by its own class """
+    order = self.hyperparams["order"]
+    n1, n2 = X1.shape[0], X2.shape[0]
+    kernel_matrices = [kern(X1[:, i:i+1], X2[:, i:i+1]) for i, kern in enumerate(self.kernel_list)]
+    ones = np.ones((n1, n2))
+    power_sum = [np.zeros((n1, n2)) for _ in range(order + 1)]
+    power_sum[0] = ones
+    for i in range(1, order + 1):
+      for matrix in kernel_matrices:
+        power_sum[i] += matrix ** i
+    esp = [np.zeros((n1, n2)) for _ in range(order + 1)]
+    esp[0] = ones
+    for m in range(1, order + 1):
+      for i in range(1, m + 1):
+        esp[m] += ((-1) ** (i - 1)) * esp[m - i] * power_sum[i]
+      esp[m] /= m
+    return self.hyperparams["scale"] * esp[order]
+
+  def __str__(self):
+    return 'ESP: order=%d, sc=%0.4f, [%s]' % (int(self.hyperparams['order']), self.hyperparams['scale'],
+                                              ', '.join(str(kern) for kern in self.kernel_list))
+
+
+def _esp_bandwidth(dim_bandwidths, i):
+  """ np.asscalar(dim_bandwidths[i]) of kernel.py:733, 741 """
+  return np.asarray(dim_bandwidths[i]).item()
+
+
+class ESPKernelSE(ESPKernel):
+  """ ESP kernel with an SE kernel for each dimension (kernel.py:729-734) """
+
+  def __init__(self, dim, scale, order, dim_bandwidths):
+    kernel_list = [SEKernel(1, 1.0, _esp_bandwidth(dim_bandwidths, i)) for i in range(dim)]
+    super(ESPKernelSE, self).__init__(scale, order, kernel_list)
+
+
+class ESPKernelMatern(ESPKernel):
+  """ ESP kernel with a Matern kernel for each dimension (kernel.py:737-742); nu is a list, one per dimension """
+
+  def __init__(self, dim, nu, scale, order, dim_bandwidths):
+    kernel_list = [MaternKernel(1, nu[i], 1.0, _esp_bandwidth(dim_bandwidths, i)) for i in range(dim)]
+    super(ESPKernelMatern, self).__init__(scale, order, kernel_list)

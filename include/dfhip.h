@@ -52,6 +52,15 @@ extern "C" {
                                * are accepted alone and as factors of a PRODUCT (sub_kind, with
                                * sub_nu = order / offset and sub_bw = scalings / powers); POLY also
                                * as a group of an ADDITIVE kernel (gp/euclidean_gp.py:870-879).    */
+#define DFH_KERNEL_ESP      6 /* dragonfly/gp/kernel.py:671-744 ESPKernel (ESPKernelSE / ESPKernelMatern):
+                               * scale * e_order(k_0, .., k_{dim-1}), the elementary symmetric
+                               * polynomial of the dim 1-D kernels k_c(x_c, y_c), by Newton-Girard
+                               * from the power sums as the reference computes it.  `scale` = ESP
+                               * scale, `nu` = order (an integer in 1..dim, at most 32 here),
+                               * n_groups = dim with group_off = 0..dim and group_dims[g] = g (one
+                               * column per group, in column order); sub_kind[g] SE | MATERN with
+                               * sub_scale / sub_nu / sub_bw that 1-D kernel's scale, nu, bandwidth;
+                               * group_factor / factor_is_sum / factor_scale NULL.               */
 
 /* One Euclidean kernel.  For SE / MATERN: `dim`, `scale`, `nu`, `bw[dim]` (dim_bandwidths); POLY /
  * EXPDECAY reuse `nu` and `bw` as described above.
