@@ -669,14 +669,14 @@ extern "C" int dfh_gp_fit(dfh_ctx* ctx, const dfh_kernel_desc* k, const double* 
     // reads nothing else; whoever asks for GP.L gets a zeroed upper part, dfh_gp_get): half the bytes of the
     // HBM-write-bound build.  DFH_KM_LOWER_ONLY=0: the full symmetric matrix as before.
     static const bool lower_env = []() { const char* e = getenv("DFH_KM_LOWER_ONLY"); return e ? atoi(e) != 0 : true; }();
+    static const bool poison_l = []() { const char* e = getenv("DFH_TEST_POISON_L"); return e && atoi(e) != 0; }();
     auto build_M = [&]() -> int {     // K + noise_var * I     (gp_core.py:843)
       SectionTimer t(ctx, DFH_T_KERNMAT);
       ctx->km_lower_only = lower_env && n >= 2048;
       // test hook (tests/test_gpu_upper_triangle_unread.py): the buffer comes recycled from the pool, and with the
       // lower-triangle-only build the tiles above the diagonal keep whatever it held -- correctness rests on no schedule
       // of the factorisation or the solves ever reading them.  DFH_TEST_POISON_L=1 fills the buffer with NaN first.
-      if (const char* e = getenv("DFH_TEST_POISON_L"); e && atoi(e) != 0)
-        DFH_HIP(hipMemsetAsync(gp->L, 0xFF, (size_t)n * n * 8, ctx->stream));
+      if (poison_l) DFH_HIP(hipMemsetAsync(gp->L, 0xFF, (size_t)n * n * 8, ctx->stream));
       const int rc = kernmat_packed(ctx, kd, 0, kd.n_parts, true, gp->Xp, gp->Np, n, gp->Xp, gp->Np, n, true, noise_var, gp->L, n);
       ctx->km_lower_only = false;
       return rc;
@@ -1844,7 +1844,6 @@ extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
   // streams): per TS block of chunk c the covariance SYRK, its stable_cholesky (latency-bound
   // look-ahead factorisation, host-synchronous because of the jitter ladder) and the draw.
   // The factorisations hide behind the next chunk's TRSM instead of idling the GPU.
-  static const bool ts_half_occ = []() { const char* e = getenv("DFH_TS_HALF_OCC"); return e ? atoi(e) != 0 : false; }();
   hipStream_t mainS = ctx->stream, bulkS = ctx->bulk;
   struct Stage1 { double* Kct; double* Xsp; double* Nsp; double* mu; };
   Stage1 st[2];
@@ -1862,12 +1861,6 @@ extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
     const int64_t i0 = c * mc_max;
     const int64_t mc = std::min(mc_max, m - i0);
     StreamSwap on_bulk(ctx, bulkS);
-    // DFH_TS_HALF_OCC=1: one workgroup per CU for the bulk GEMMs so the other half of each CU stays
-    // free for the latency-bound factorisation kernels of stage 2.  Off by default: with the blocks
-    // of a chunk factored as one batch the latency-bound share is small and the ~14% the bulk GEMMs
-    // lose at half occupancy costs more than the overlap returns (measured 1602 vs 1495 ms/step).
-    struct HalfOcc { dfh_ctx* c; bool old; HalfOcc(dfh_ctx* x, bool v) : c(x), old(x->gemm_half_occupancy) { c->gemm_half_occupancy = v; }
-                     ~HalfOcc() { c->gemm_half_occupancy = old; } } half(ctx, nchunks > 1 && ts_half_occ);
     if (c >= 2) DFH_HIP(hipStreamWaitEvent(bulkS, ev_free[p], 0));   // parity buffers released by stage 2
     const double* xs_c = nullptr;
     if (xs_dev) xs_c = Xs + i0 * gp->d;

@@ -1062,12 +1062,12 @@ __global__ __launch_bounds__(256, 1) void panel_strip_kernel(const double* __res
 //   strip s:  for j < s: wait for L_jj, X_sj = (A_sj - ...) L_jj^-T, update the blocks (j, s];
 //             then factor its own 64 x 64 diagonal block (factor64_waves) and publish L_ss,
 // handing data on through HBM with two sets of per-matrix counters: flag[s] = epoch once L_ss and
-// the inverses of its 16 x 16 blocks are out, prog[s] = j + 1 once X_sj is.  Readers spin on the
-// counter (relaxed agent-scope loads, then one acquire fence), writers publish with a barrier and a
-// release store.  Workgroups only ever wait for workgroups with a smaller index of the same launch,
-// which the dispatcher starts first.  This replaces the sixteen dependent launches of a panel
-// (eight pivot steps, eight K = 64 updates) whose gaps and HBM round trips were the factorisation's
-// chain.
+// the inverses of its 16 x 16 blocks are out, prog[s] = j + 1 once X_sj is.  What is handed over goes
+// out with write-through stores and comes in with agent-coherent loads (sc1); the counters are relaxed
+// atomics: no cache-wide maintenance on the chain.  Workgroups only ever wait for workgroups with a
+// smaller index of the same launch, which the dispatcher starts first.  This replaces the sixteen
+// dependent launches of a panel (eight pivot steps, eight K = 64 updates) whose gaps and HBM round
+// trips were the factorisation's chain.
 constexpr int FUSED_SYNC_INTS = 24;
 struct FusedArgs {
   double* D; long lda;
@@ -1084,13 +1084,7 @@ struct FusedArgs {
   // started in *resident, and -- wait_ptr != null -- only then waits for *wait_ptr >= wait_target
   // (the trailing update of another stream has written the diagonal block) before touching the matrix
   int* resident; const int* wait_ptr; int wait_target;
-  // hand-off protocol inside the launch.  0: plain stores + release fence (buffer_wbl2: the XCD's whole L2 is
-  // written back, dirty C tiles of a trailing update running beside the panel included) / acquire fence
-  // (buffer_inv) + plain loads.  1: what is handed over goes out with write-through stores and comes in
-  // with agent-coherent loads (sc1), the flags are relaxed: no cache-wide maintenance on the chain.
-  int sc1;
   int prog_sleep;               // s_sleep argument of the polls that are not on the chain (waits for another strip's X_cJ)
-  int g0;                       // strip index of the launch's first workgroup (0; or 8: a launch of the rows-below strips alone)
 #ifdef DFH_DEBUG_HOOKS
   long long* stamps = nullptr;  // dfh_debug_panel_stamps: [strip][64] s_memrealtime (100 MHz) at the points marked FSTAMP
 #endif
@@ -1119,19 +1113,9 @@ __device__ __forceinline__ void fused_wait(const int* p, int target, const Fused
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // later loads see what the writer released
 }
 
-__device__ __forceinline__ void fused_publish(int* p, int value) {
-  __syncthreads();                                    // every wave's stores are issued and acknowledged
-  if (threadIdx.x == 0) __hip_atomic_store(p, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the sc1 protocol (FusedArgs::sc1): data with write-through stores / agent-coherent loads ...
-__device__ __forceinline__ void st_out(double* p, double v, bool sc1) {
-  if (sc1) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p = v;
-}
-__device__ __forceinline__ double ld_in(const double* p, bool sc1) {
-  return sc1 ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
+// the sc1 protocol of the one-launch panel: data with write-through stores / agent-coherent loads ...
+__device__ __forceinline__ void st_out(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double ld_in(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // ... the flag goes up once every wave's write-through stores have been acknowledged (s_barrier alone does not
 // wait for outstanding stores on gfx950: each wave drains its own first), and is read without a fence
 __device__ __forceinline__ void fused_publish_sc1(int* p, int value) {
@@ -1158,92 +1142,7 @@ __device__ __forceinline__ void fused_wait_sc1(const int* p, int target, const F
   __syncthreads();
 }
 
-template <int J>
-__device__ __forceinline__ void fused_step(const FusedArgs& a, double4_t (&acc)[32], int s, bool diag, double* Rw,
-                                           long rows_left, double* ssm) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int kq = lane >> 4, l15 = lane & 15;
-  double* Lj = ssm;                                                // [64][SK_LD]
-  double* Lc = ssm + PB * SK_LD;                                   // [64][SK_LD]
-  double* Xall = ssm + 2 * PB * SK_LD;                             // [64][SK_LD]: the four waves' solved rows
-  double* Xw = Xall + w * (16 * SK_LD);
-  double* Tt = ssm + 2 * PB * SK_LD + 4 * 16 * SK_LD + w * (16 * SK_TD);
-  double* li = ssm + 2 * PB * SK_LD + 4 * 16 * SK_LD + 4 * 16 * SK_TD;
-  int* flag = a.sync; int* prog = a.sync + 8;
-  if (J < s) {
-    fused_wait(flag + J, a.epoch, a);
-    FSTAMP(a, blockIdx.x + a.g0, 1 + 4 * J);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) Lj[(w + 4 * r) * SK_LD + lane] = a.Lfac[J * PB * PB + (w + 4 * r) * PB + lane];
-    for (int i = tid; i < 4 * 16 * 16; i += 256)
-      li[(i >> 8) * (16 * SK_TD) + ((i >> 4) & 15) * SK_TD + (i & 15)] =
-          a.Linv16[J * (4 * 16 * 17) + (i >> 8) * (16 * 17) + ((i >> 4) & 15) * 17 + (i & 15)];
-    __syncthreads();
-    FSTAMP(a, blockIdx.x + a.g0, 2 + 4 * J);
-    // ---- row solve of block J (as in panel_strip_kernel) ----
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      double4_t a1 = acc[4 * J + b], a2 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int bp = 0; bp < b; ++bp)
-#pragma unroll
-        for (int st = 0; st < 4; ++st) {
-          const double av = Xw[l15 * SK_LD + 16 * bp + 4 * st + kq];
-          const double bv = -Lj[(16 * b + l15) * SK_LD + 16 * bp + 4 * st + kq];
-          if (st & 1) a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, a2, 0, 0, 0);
-          else a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, a1, 0, 0, 0);
-        }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Tt[(kq + 4 * r) * SK_TD + l15] = a1[r] + a2[r];
-      COMPILER_BARRIER();
-      double4_t x = {0.0, 0.0, 0.0, 0.0}, x2 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int st = 0; st < 4; ++st) {
-        const double av = Tt[l15 * SK_TD + 4 * st + kq];
-        const double bv = li[b * (16 * SK_TD) + l15 * SK_TD + 4 * st + kq];
-        if (st & 1) x2 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, x2, 0, 0, 0);
-        else x = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, x, 0, 0, 0);
-      }
-      COMPILER_BARRIER();
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Xw[(kq + 4 * r) * SK_LD + 16 * b + l15] = x[r] + x2[r];
-      COMPILER_BARRIER();
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (i < rows_left) Rw[(long)i * a.lda + J * PB + lane] = Xw[i * SK_LD + lane];
-    if (diag) fused_publish(prog + s, a.epoch * 16 + J + 1);   // X_sJ is out (later diagonal strips and the rows below read it)
-    FSTAMP(a, blockIdx.x + a.g0, 3 + 4 * J);
-    double xa[16];
-#pragma unroll
-    for (int st = 0; st < 16; ++st) xa[st] = -Xw[l15 * SK_LD + 4 * st + kq];
-    const int c_hi = diag ? s : 7;                     // last block this strip still needs
-#pragma unroll
-    for (int c = J + 1; c < 8; ++c) {
-      if (c > c_hi) break;
-      const double* L;
-      if (diag && c == s) {
-        __syncthreads();                               // all four waves' rows of X_sJ are in Xall
-        L = Xall;                                      // own diagonal block: A_ss -= X_sJ X_sJ^T
-      } else {
-        fused_wait(prog + c, a.epoch * 16 + J + 1, a); // strip c has published X_cJ (its barrier also frees Lc)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          Lc[(w + 4 * r) * SK_LD + lane] = a.D[(long)(c * PB + w + 4 * r) * a.lda + J * PB + lane];
-        __syncthreads();
-        L = Lc;
-      }
-#pragma unroll
-      for (int i = 0; i < 64; ++i)
-        acc[4 * c + (i & 3)] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[i >> 2], L[(16 * (i & 3) + l15) * SK_LD + 4 * (i >> 2) + kq],
-                                                                    acc[4 * c + (i & 3)], 0, 0, 0);
-    }
-    __syncthreads();                                   // Xall / Lj / li are free for the next step
-    FSTAMP(a, blockIdx.x + a.g0, 4 + 4 * J);
-  }
-}
-
-// Round 4: the same step with the strip held TRANSPOSED in the accumulators,
+// One column step J of a strip (round 4), the strip held TRANSPOSED in the accumulators,
 //     accT[t][r] of lane (kq, l15) = strip element (row l15 of the wave's 16, column 16 t + kq + 4 r),
 // i.e. the D layout of v_mfma_f64_16x16x4 for the transposed tile: D[kq + 4 r][l15] = T[l15][kq + 4 r].  In
 // that layout an accumulator tile IS the B operand of a product that contracts over the strip's columns
@@ -1251,7 +1150,7 @@ __device__ __forceinline__ void fused_step(const FusedArgs& a, double4_t (&acc)[
 //     X_b^T = Linv_bb T_b^T,     T_b'^T -= L_b'b X_b^T  (b' > b, right-looking),     A_c^T -= L_cJ X^T
 // take their A operands (rows of L / Linv, one ds_read_b64 per lane) from LDS and their B operands straight
 // from registers: the row solve no longer changes layout through LDS between its four 16-column stages.
-// Measured on the row-per-accumulator form (tools/dbg_panel.py, 100 MHz stamps): 4.25 us of a 22.5 us hop
+// Measured on the round-3 row-per-accumulator form (tools/dbg_panel.py, 100 MHz stamps): 4.25 us of a 22.5 us hop
 // were this solve -- 40 MFMAs at ~200 cycles each, eight LDS write -> read round trips.
 // acc^T[4 C + i] -= L_i X^T over the k-steps [KS0, KS1) of a 64-column block (k-step ks: columns 4 ks + kq of
 // X = -xn), i = 0 .. 3: the order of panel_strip_kernel's update (k-step outer, the four tiles inner, ONE
@@ -1289,20 +1188,20 @@ __device__ __forceinline__ void fused_step_t(const FusedArgs& a, double4_t (&acc
   double* Lc = ssm + PB * SK_LD;                                   // [64][SK_LD]
   double* Xall = ssm + 2 * PB * SK_LD;                             // [64][SK_LD]: the four waves' solved rows
   double* Xw = Xall + w * (16 * SK_LD);
+  // (the [4][16][SK_TD] before li is unused: the round-3 step's transpose buffer, still reserved in FUSED_SMEM)
   double* li = ssm + 2 * PB * SK_LD + 4 * 16 * SK_LD + 4 * 16 * SK_TD;
   int* flag = a.sync; int* prog = a.sync + 8;
-  constexpr bool sc1 = true;        // the transposed panel always hands over with write-through stores / coherent loads
   if (J < s) {
     fused_wait_sc1(flag + J, a.epoch, a, !(diag && J == s - 1));
-    FSTAMP(a, blockIdx.x + a.g0, 1 + 4 * J);
+    FSTAMP(a, blockIdx.x, 1 + 4 * J);
     {
       double pre[16], prei[4];                         // all loads in flight before the first LDS write
 #pragma unroll
-      for (int r = 0; r < 16; ++r) pre[r] = ld_in(a.Lfac + J * PB * PB + (w + 4 * r) * PB + lane, sc1);
+      for (int r = 0; r < 16; ++r) pre[r] = ld_in(a.Lfac + J * PB * PB + (w + 4 * r) * PB + lane);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = tid + 256 * r;
-        prei[r] = ld_in(a.Linv16 + J * (4 * 16 * 17) + (i >> 8) * (16 * 17) + ((i >> 4) & 15) * 17 + (i & 15), sc1);
+        prei[r] = ld_in(a.Linv16 + J * (4 * 16 * 17) + (i >> 8) * (16 * 17) + ((i >> 4) & 15) * 17 + (i & 15));
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) Lj[(w + 4 * r) * SK_LD + lane] = pre[r];
@@ -1313,7 +1212,7 @@ __device__ __forceinline__ void fused_step_t(const FusedArgs& a, double4_t (&acc
       }
     }
     __syncthreads();
-    FSTAMP(a, blockIdx.x + a.g0, 2 + 4 * J);
+    FSTAMP(a, blockIdx.x, 2 + 4 * J);
     // ---- row solve of block J, 16-column stages, right-looking; xn[b] = -X_b^T ----
     // (the accumulator tiles of block J are only ever read from here on: the solved block lives in xn and in LDS, so
     //  that no accumulator tile is written by the vector unit -- they stay in the AGPR half of the register file)
@@ -1327,14 +1226,14 @@ __device__ __forceinline__ void fused_step_t(const FusedArgs& a, double4_t (&acc
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       if (b == 3 && last_step) {
-        FSTAMP(a, blockIdx.x + a.g0, 48);
+        FSTAMP(a, blockIdx.x, 48);
         __syncthreads();                               // columns 0 .. 47 of all four waves' X_sJ are in Xall
-        FSTAMP(a, blockIdx.x + a.g0, 49);
+        FSTAMP(a, blockIdx.x, 49);
         if constexpr (J + 1 < 8) strip_update_t<0, 12>(acc, J + 1, Xall, xn, l15, kq);
       }
-      if (b == 3 && last_step) FSTAMP(a, blockIdx.x + a.g0, 50);
+      if (b == 3 && last_step) FSTAMP(a, blockIdx.x, 50);
       // T_b^T = the tile (which carries the even-numbered k-steps of the earlier stages' updates) + the odd chain:
-      // the association of panel_strip_kernel / diag_step64_kernel / fused_step (two accumulators per product,
+      // the association of panel_strip_kernel / diag_step64_kernel (two accumulators per product,
       // added at the end), so that every schedule of the factorisation rounds alike -- results do not depend on
       // how a candidate set is cut into shards, chunks and lock-step groups (tests/test_gpu_mgpu.py).
       // It leaves the accumulator file for the vector registers here: the tile is dead from now on, so the
@@ -1360,9 +1259,9 @@ __device__ __forceinline__ void fused_step_t(const FusedArgs& a, double4_t (&acc
         // (the inverse's loads below are coherent loads issued after the poll in program order; the compiler must
         //  not move them above it either)
         asm volatile("" ::: "memory");
-        if (last_step) FSTAMP(a, blockIdx.x + a.g0, 51);
+        if (last_step) FSTAMP(a, blockIdx.x, 51);
         const double* gi = a.Linv16 + J * (4 * 16 * 17) + 3 * (16 * 17) + l15 * 17 + kq;
-        i0 = ld_in(gi, sc1); i1 = ld_in(gi + 4, sc1); i2 = ld_in(gi + 8, sc1); i3 = ld_in(gi + 12, sc1);
+        i0 = ld_in(gi); i1 = ld_in(gi + 4); i2 = ld_in(gi + 8); i3 = ld_in(gi + 12);
       }
       double4_t p = {0.0, 0.0, 0.0, 0.0}, p2 = {0.0, 0.0, 0.0, 0.0};
       p = __builtin_amdgcn_mfma_f64_16x16x4f64(i0, tb0, p, 0, 0, 0);
@@ -1386,17 +1285,17 @@ __device__ __forceinline__ void fused_step_t(const FusedArgs& a, double4_t (&acc
     COMPILER_BARRIER();                              // same wave: LDS executes its operations in order
     if (rows_left >= 16) {                             // (wave-uniform)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) st_out(Rw + (long)i * a.lda + J * PB + lane, Xw[i * SK_LD + lane], sc1);
+      for (int i = 0; i < 16; ++i) st_out(Rw + (long)i * a.lda + J * PB + lane, Xw[i * SK_LD + lane]);
     } else {
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-        if (i < rows_left) st_out(Rw + (long)i * a.lda + J * PB + lane, Xw[i * SK_LD + lane], sc1);
+        if (i < rows_left) st_out(Rw + (long)i * a.lda + J * PB + lane, Xw[i * SK_LD + lane]);
     }
     // X_sJ is out (later diagonal strips and the rows below read it).  In the strip's LAST step -- the one on the
     // chain -- the announcement waits until the own-block product below has been issued: nobody needs X_s,s-1
     // before L_ss exists, and the wait for the stores' acknowledgement (1.5 us) leaves the chain.
     if (diag && !last_step) fused_publish_sc1(prog + s, a.epoch * 16 + J + 1);
-    FSTAMP(a, blockIdx.x + a.g0, 3 + 4 * J);
+    FSTAMP(a, blockIdx.x, 3 + 4 * J);
     const int c_hi = diag ? s : 7;                     // last block this strip still needs
 #pragma unroll
     for (int c = J + 1; c < 8; ++c) {
@@ -1404,16 +1303,16 @@ __device__ __forceinline__ void fused_step_t(const FusedArgs& a, double4_t (&acc
       const double* L;
       const bool own = diag && c == s;
       if (own) {
-        if (last_step) FSTAMP(a, blockIdx.x + a.g0, 52);
+        if (last_step) FSTAMP(a, blockIdx.x, 52);
         __syncthreads();                               // all four waves' rows of X_sJ are in Xall
-        if (last_step) FSTAMP(a, blockIdx.x + a.g0, 53);
+        if (last_step) FSTAMP(a, blockIdx.x, 53);
         L = Xall;                                      // own diagonal block: A_ss -= X_sJ X_sJ^T (lower tiles only)
       } else {
         // strip c has published X_cJ (its barrier also frees Lc)
         fused_wait_sc1(prog + c, a.epoch * 16 + J + 1, a, true);
         double pre[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) pre[r] = ld_in(a.D + (long)(c * PB + w + 4 * r) * a.lda + J * PB + lane, sc1);
+        for (int r = 0; r < 16; ++r) pre[r] = ld_in(a.D + (long)(c * PB + w + 4 * r) * a.lda + J * PB + lane);
 #pragma unroll
         for (int r = 0; r < 16; ++r) Lc[(w + 4 * r) * SK_LD + lane] = pre[r];
         __syncthreads();
@@ -1426,13 +1325,12 @@ __device__ __forceinline__ void fused_step_t(const FusedArgs& a, double4_t (&acc
     }
     // (the last step's X_s,s-1 is announced from the kernel's tail, behind the staging barrier: by then the
     //  stores' acknowledgement, 1.5 - 2 us for write-through, has arrived without anybody waiting for it)
-    if (last_step) FSTAMP(a, blockIdx.x + a.g0, 54);
+    if (last_step) FSTAMP(a, blockIdx.x, 54);
     __syncthreads();                                   // Xall / Lj / li are free for the next step
-    FSTAMP(a, blockIdx.x + a.g0, 4 + 4 * J);
+    FSTAMP(a, blockIdx.x, 4 + 4 * J);
   }
 }
 
-template <bool TR>
 __global__ __launch_bounds__(256, 1) void panel_fused_kernel(FusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) double ssm[];
   a.D += (long)blockIdx.y * a.strideD;
@@ -1452,9 +1350,8 @@ __global__ __launch_bounds__(256, 1) void panel_fused_kernel(FusedArgs a) {
   //  read) in every function of the built library and tests/test_isa_audit.py runs that on each build.)
   const int w = tid >> 6;
   const int kq = lane >> 4, l15 = lane & 15;
-  const int g = blockIdx.x + a.g0;   // (g0: the launch may hold only the rows-below strips, see cholesky_device_impl)
+  const int g = blockIdx.x;
   const int nd = (a.nbk + PB - 1) / PB;              // diagonal strips (8 for a full panel)
-  if (TR) a.sc1 = 1;                                 // the transposed panel's hand-offs are write-through / coherent loads
   if (a.resident) {
     if (tid == 0) __hip_atomic_fetch_add(a.resident, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (a.wait_ptr) fused_wait(a.wait_ptr, a.wait_target, a, SYNC_ST_GATE);
@@ -1464,8 +1361,8 @@ __global__ __launch_bounds__(256, 1) void panel_fused_kernel(FusedArgs a) {
   double* Rw = a.D + ((long)g * PB + 16 * w) * a.lda;               // this wave's 16 rows of the panel
   const long rows_left = (long)(a.nbk + a.rows_below) - ((long)g * PB + 16 * w);
   double4_t acc[32];
-  const bool full_tr = TR && a.nbk == 8 * PB && rows_left >= 16;      // (wave-uniform)
-  if (full_tr) {
+  const bool full = a.nbk == 8 * PB && rows_left >= 16;      // (wave-uniform)
+  if (full) {
     // full panel, all sixteen rows present: one base address per lane and immediate offsets; the blocks a
     // diagonal strip never touches are not loaded, its own block is cut to the lower triangle
     const double* rp = Rw + (long)l15 * a.lda + kq;
@@ -1493,9 +1390,9 @@ __global__ __launch_bounds__(256, 1) void panel_fused_kernel(FusedArgs a) {
   for (int t = 0; t < 32; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      // TR: lane (kq, l15) holds row l15, columns 16 t + kq + 4 r; otherwise rows kq + 4 r, column 16 t + l15
-      const int rl = TR ? l15 : kq + 4 * r;              // row within the wave's 16
-      const int cl = TR ? kq + 4 * r : l15;              // column within the 16-column tile
+      // lane (kq, l15) holds row l15, columns 16 t + kq + 4 r
+      const int rl = l15;                                // row within the wave's 16
+      const int cl = kq + 4 * r;                         // column within the 16-column tile
       const int row = 16 * w + rl, c = t >> 2, col = 16 * (t & 3) + cl;
       // a diagonal strip needs its blocks up to its own, of that one only the lower triangle; rows and
       // columns beyond the block's order (last panel) are identity padding
@@ -1504,25 +1401,14 @@ __global__ __launch_bounds__(256, 1) void panel_fused_kernel(FusedArgs a) {
       acc[t][r] = want ? Rw[(long)rl * a.lda + 16 * t + cl] : (pad_one ? 1.0 : 0.0);
     }
   FSTAMP(a, g, 0);
-  if constexpr (TR) {
-    fused_step_t<0>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step_t<1>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step_t<2>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step_t<3>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step_t<4>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step_t<5>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step_t<6>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step_t<7>(a, acc, s, diag, Rw, rows_left, ssm);
-  } else {
-    fused_step<0>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step<1>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step<2>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step<3>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step<4>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step<5>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step<6>(a, acc, s, diag, Rw, rows_left, ssm);
-    fused_step<7>(a, acc, s, diag, Rw, rows_left, ssm);
-  }
+  fused_step_t<0>(a, acc, s, diag, Rw, rows_left, ssm);
+  fused_step_t<1>(a, acc, s, diag, Rw, rows_left, ssm);
+  fused_step_t<2>(a, acc, s, diag, Rw, rows_left, ssm);
+  fused_step_t<3>(a, acc, s, diag, Rw, rows_left, ssm);
+  fused_step_t<4>(a, acc, s, diag, Rw, rows_left, ssm);
+  fused_step_t<5>(a, acc, s, diag, Rw, rows_left, ssm);
+  fused_step_t<6>(a, acc, s, diag, Rw, rows_left, ssm);
+  fused_step_t<7>(a, acc, s, diag, Rw, rows_left, ssm);
   if (!diag) return;
   // ---- factor the strip's own diagonal block and publish it (LDS of the strip machinery is free) ----
   double* Sp = ssm;                                  // [64][SPP] staged block, then the factor image
@@ -1547,23 +1433,23 @@ __global__ __launch_bounds__(256, 1) void panel_fused_kernel(FusedArgs a) {
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = 16 * w + (TR ? l15 : kq + 4 * r), col = 16 * t4 + (TR ? kq + 4 * r : l15);
+      const int row = 16 * w + l15, col = 16 * t4 + kq + 4 * r;
       Sp[row * SPP + col] = (col <= row) ? v[r] : 0.0;
     }
   }
   if (tid < PB) ring[tid * PB] = 0.0;
-  if (TR && s > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows of X_s,s-1 are out
+  if (s > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows of X_s,s-1 are out
   __syncthreads();
-  if (TR && s > 0 && tid == 0)                         // ... all four waves': announce them (see fused_step_t)
+  if (s > 0 && tid == 0)                         // ... all four waves': announce them (see fused_step_t)
     __hip_atomic_store(a.sync + 8 + s, a.epoch * 16 + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   FSTAMP(a, g, 40);
   double av[16];
   double* tbuf = tbuf0 + (w > 0 ? (w - 1) : 0) * PB * 17;
-  // TR: the inverse of the last 16 x 16 block -- the only one of the four that is not hidden behind later columns,
+  // The inverse of the last 16 x 16 block -- the only one of the four that is not hidden behind later columns,
   // ~4.3k cycles at the end of the chain -- is computed AFTER the factor has been handed on, and published under a
   // second flag: the next strip needs it for the last of its four solve stages only, ~3 us after it saw the first
   double my_r3 = 1.0;
-  const int bad = factor64_waves<TR>(av, lane, w, Sp, tbuf, ring, lbb, linv, rdiag, &s_ring_timeout, nullptr, &my_r3);
+  const int bad = factor64_waves<true>(av, lane, w, Sp, tbuf, ring, lbb, linv, rdiag, &s_ring_timeout, nullptr, &my_r3);
   if (lane == 0) s_badv[w] = bad;
 #pragma unroll
   for (int j = 0; j < 16; ++j) Sp[lane * SPP + perm16(16 * w + j)] = av[j];
@@ -1582,24 +1468,21 @@ __global__ __launch_bounds__(256, 1) void panel_fused_kernel(FusedArgs a) {
   {
     double* Lout = a.Lfac + (long)s * PB * PB;
     const int pk = perm16(lane);
-    const bool sc1 = TR || a.sc1 != 0;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) st_out(Lout + (w + 4 * r) * PB + lane, Sp[(w + 4 * r) * SPP + pk], sc1);
+    for (int r = 0; r < 16; ++r) st_out(Lout + (w + 4 * r) * PB + lane, Sp[(w + 4 * r) * SPP + pk]);
     double* Iout = a.Linv16 + (long)s * (4 * 16 * 17);
-    for (int i = tid; i < (TR ? 3 : 4) * 16 * 17; i += 256) st_out(Iout + i, linv[i], sc1);
+    for (int i = tid; i < 3 * 16 * 17; i += 256) st_out(Iout + i, linv[i]);
   }
   // published even after a failed pivot: nobody may hang
-  if (TR || a.sc1) fused_publish_sc1(a.sync + s, a.epoch); else fused_publish(a.sync + s, a.epoch);
+  fused_publish_sc1(a.sync + s, a.epoch);
   FSTAMP(a, g, 43);
-  if constexpr (TR) {
-    if (w == 3) {
-      factor64_inverse16(av, lane, 3, lbb, linv, rdiag, my_r3);
-      COMPILER_BARRIER();                              // same wave: LDS executes its operations in order
-      double* Iout3 = a.Linv16 + (long)s * (4 * 16 * 17) + 3 * (16 * 17);
-      for (int i = lane; i < 16 * 17; i += 64) st_out(Iout3 + i, linv[3 * (16 * 17) + i], true);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the whole wave's stores are acknowledged
-      if (lane == 0) __hip_atomic_store(a.sync + 16 + s, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+  if (w == 3) {
+    factor64_inverse16(av, lane, 3, lbb, linv, rdiag, my_r3);
+    COMPILER_BARRIER();                              // same wave: LDS executes its operations in order
+    double* Iout3 = a.Linv16 + (long)s * (4 * 16 * 17) + 3 * (16 * 17);
+    for (int i = lane; i < 16 * 17; i += 64) st_out(Iout3 + i, linv[3 * (16 * 17) + i]);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the whole wave's stores are acknowledged
+    if (lane == 0) __hip_atomic_store(a.sync + 16 + s, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -1935,11 +1818,6 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
   static const int fused_max_batch_env = []() { const char* e = getenv("DFH_CHOL_FUSED_MAX_BATCH"); return e ? atoi(e) : -1; }();
   const int fused_max_batch = fused_max_batch_env >= 0 ? fused_max_batch_env : (n <= 2048 ? 64 : 32);
   const bool fused_mode = fused_on && nbatch <= fused_max_batch && !safe;   // safe: no inter-workgroup hand-offs
-  // DFH_CHOL_FUSED_TR=0: the round-3 form of the one-launch panel (strip rows in the accumulators' rows)
-  static const bool fused_tr = env_int("DFH_CHOL_FUSED_TR", 1) != 0;
-  void (*const fused_kernel)(FusedArgs) = fused_tr ? panel_fused_kernel<true> : panel_fused_kernel<false>;
-  // DFH_CHOL_FUSED_SC1=0: hand-offs inside the launch with release / acquire fences (FusedArgs::sc1)
-  static const int fused_sc1 = env_int("DFH_CHOL_FUSED_SC1", 1) != 0 ? 1 : 0;
   static const int fused_prog_sleep = env_int("DFH_CHOL_PROG_SLEEP", 8);
   if (fused_mode) DFH_HIP(hipMemsetAsync(fsync_all, 0, (size_t)nbatch * FUSED_SYNC_INTS * sizeof(int), ctx->stream));
   // Panel strips (panel_strip_kernel) for lock-step batches: there the pivot steps are throughput-bound
@@ -1971,9 +1849,7 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_STEP_SMEM));
     DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_strip_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, STRIP_SMEM));
-    DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_fused_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_SMEM));
-    DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_fused_kernel<true>),
+    DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_fused_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_SMEM));
     attr_set = true;
   }
@@ -2005,7 +1881,6 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
   DFH_HIP(hipEventRecord(ev_start, M));
   DFH_HIP(hipStreamWaitEvent(P, ev_start, 0));
   DFH_HIP(hipStreamWaitEvent(X, ev_start, 0));
-  if (ctx->bulk_normal) DFH_HIP(hipStreamWaitEvent(ctx->bulk_normal, ev_start, 0));
 
   for (int64_t kb = 0; kb < nblk; ++kb) {
     const int64_t k0 = kb * NB;
@@ -2060,13 +1935,11 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
     if (kb < kb_lr) {
       // =============== resident look-ahead panel (see the comment above cholesky_device_impl) ===============
       int* sy = lr_sync + 4 * kb;
-      static const bool lr_chain_normal_prio = env_int("DFH_CHOL_LR_NORMAL_PRIO", 0) != 0;
-      hipStream_t Pc = lr_chain_normal_prio ? ctx->bulk_normal : P;
       double* A21 = A + (k0 + NB) * lda + k0;          // rem x 512: the rows below the diagonal block
       double* Xk = lr_X + (kb & 1) * lr_xstride;
       {
-        StreamSwap on_p(ctx, Pc);
-        if (e_aux_prev2) DFH_HIP(hipStreamWaitEvent(Pc, e_aux_prev2, 0));     // factor scratch of this parity is free again
+        StreamSwap on_p(ctx, P);
+        if (e_aux_prev2) DFH_HIP(hipStreamWaitEvent(P, e_aux_prev2, 0));     // factor scratch of this parity is free again
         // Not before update(kb-2) has finished: the eight workgroups need whole CUs, and a high-priority
         // launch that is PENDING because it does not fit throttles the dispatch of the running update
         // (measured: update(0) 2.42 ms with this launch enqueued after it, 2.52 / 2.71 ms with it pending
@@ -2074,38 +1947,38 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
         if (kb >= 2) {
           hipEvent_t e_trail_prev2;
           DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 3 + 5 * (kb - 2), &e_trail_prev2));
-          DFH_HIP(hipStreamWaitEvent(Pc, e_trail_prev2, 0));
+          DFH_HIP(hipStreamWaitEvent(P, e_trail_prev2, 0));
         }
         FusedArgs fa;
         fa.D = D; fa.lda = lda; fa.Lfac = Lscr; fa.Linv16 = Iscr; fa.sync = fsync_all; fa.epoch = (int)kb + 1;
         fa.nbk = (int)NB; fa.rows_below = 0; fa.info = d_info; fa.pivot_base = (long)k0;
         fa.strideD = strideA; fa.strideL = strideL; fa.strideI = strideI;
         fa.status = d_status; fa.spin_limit = spin_limit;
-        fa.sc1 = fused_sc1; fa.prog_sleep = fused_prog_sleep; fa.g0 = 0;
+        fa.prog_sleep = fused_prog_sleep;
         fa.resident = sy;
         fa.wait_ptr = kb > 0 ? sy - 4 + 1 : nullptr;   // the sixteen... ten lower tiles of this diagonal block, out of update(kb-1)
         fa.wait_target = 10;
-        hipLaunchKernelGGL(fused_kernel, dim3((unsigned)(NB / PB), 1), dim3(256), FUSED_SMEM, Pc, fa);
+        hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)(NB / PB), 1), dim3(256), FUSED_SMEM, P, fa);
         DFH_LAUNCH_CHECK();
-        DFH_HIP(hipEventRecord(e_diag, Pc));
+        DFH_HIP(hipEventRecord(e_diag, P));
       }
       // the inverse is ON the chain here (the panel solve multiplies by it): it runs on the priority
       // stream -- on the auxiliary stream its small kernels wait for a slot behind the trailing update's
       // pending workgroups (trtri64: 36 us alone, 1.3 - 1.8 ms beside the update)
-      DFH_TRY(aux_block(nullptr, Pc));
+      DFH_TRY(aux_block(nullptr, P));
       {
-        StreamSwap on_p(ctx, Pc);
+        StreamSwap on_p(ctx, P);
         if (kb > 0) {
           // the whole block column has to be out of update(kb-1): 4 T - 6 look-ahead tiles over T tile rows
           const int64_t Tprev = (rem + NB + 127) / 128;
-          hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, Pc, (const int*)(sy - 4 + 2), (int)(4 * Tprev - 6), d_status, spin_limit);
+          hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, P, (const int*)(sy - 4 + 2), (int)(4 * Tprev - 6), d_status, spin_limit);
           DFH_LAUNCH_CHECK();
         }
         const double* Mi = Linv;                               // inverse of the diagonal block (lower, ld NB)
         const double* Lbb = Linv + clean_blocks * NB * NB;      // its clean copy
         // the solved rows go to a panel buffer of their own (two, alternating): the trailing update reads
         // them from there (contiguous, ld 512) and the copy into the factor happens off the chain
-        if (e_copy_prev2) DFH_HIP(hipStreamWaitEvent(Pc, e_copy_prev2, 0));      // the buffer's previous contents are in place
+        if (e_copy_prev2) DFH_HIP(hipStreamWaitEvent(P, e_copy_prev2, 0));      // the buffer's previous contents are in place
         DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, rem, NB, NB, 1.0, A21, lda, Mi, NB, 0.0, nullptr, 0, Xk, NB));
         for (int st = 0; st < LR_REFINE_MAX; ++st) {
           // X <- X + (A21 - X L_bb^T) M^T, the right-hand side untouched; skipped on the device unless due
@@ -2116,9 +1989,7 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
           ctx->gemm_cond = nullptr;
           DFH_TRY(rc_r);
         }
-        static const bool lr_inplace = env_int("DFH_CHOL_LR_INPLACE", 0) != 0;     // ablation: operands of the update in place
-        if (lr_inplace) DFH_TRY(copy_matrix(ctx, Xk, NB, A21, lda, rem, NB));
-        DFH_HIP(hipEventRecord(e_panel, Pc));
+        DFH_HIP(hipEventRecord(e_panel, P));
       }
       {
         StreamSwap on_x(ctx, X);
@@ -2136,10 +2007,7 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
       {
         double* C = A + (k0 + NB) * lda + (k0 + NB);
         ctx->gemm_la_cnt = next_resident ? sy + 1 : nullptr;
-        static const bool lr_inplace_u = env_int("DFH_CHOL_LR_INPLACE", 0) != 0;
-        const double* Uop = lr_inplace_u ? A21 : Xk;
-        const int64_t ldu = lr_inplace_u ? lda : NB;
-        const int rc_u = gemm_f64(ctx, GEMM_LOWER, rem, rem, NB, -1.0, Uop, ldu, Uop, ldu, 1.0, C, lda, C, lda);
+        const int rc_u = gemm_f64(ctx, GEMM_LOWER, rem, rem, NB, -1.0, Xk, NB, Xk, NB, 1.0, C, lda, C, lda);
         ctx->gemm_la_cnt = nullptr;
         DFH_TRY(rc_u);
       }
@@ -2157,19 +2025,6 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
         if (e_copy_prev2) DFH_HIP(hipStreamWaitEvent(P, e_copy_prev2, 0));
       }
       const bool fused = fused_mode;                  // full panels, and the (last) partial one: identity padding
-      // (experiment, default OFF: measured slower -- n = 4096 2.16 -> 2.81 ms, 8192 6.28 -> 8.97 -- because the
-      //  rows-below launch on a normal-priority stream queues behind the trailing update's pending workgroups,
-      //  and a second high-priority stream made every schedule slower, presumably by sharing hardware queues;
-      //  tools/r4_run24.sh, docs/NOTES_r04.md)
-      static const bool split_on = env_int("DFH_CHOL_FUSED_SPLIT", 0) != 0;
-      const bool split = fused && split_on && nbatch == 1 && nbk == NB && rem > 0;
-      hipStream_t Q = ctx->bulk_normal;
-      // Experiment switch (off): no look-ahead at all above DFH_CHOL_SERIAL_MIN_REM rows -- the one-launch
-      // panel cannot be placed while the update runs and, pending, slows it (K = 1024 updates at 52 TF/s
-      // against 64 alone); starting it only when the update has finished nevertheless LOSES (n = 16384
-      // 34.5 -> 35.1 ms, 8192 7.06 -> 7.9): the panel does overlap the update's last wave of tiles.
-      static const long serial_min_rem = env_int("DFH_CHOL_SERIAL_MIN_REM", 1 << 30);
-      if (fused && kb > 0 && e_trail_prev && rem + nbk > serial_min_rem) DFH_HIP(hipStreamWaitEvent(P, e_trail_prev, 0));
       if (fused) {
         // ---- the whole panel in one launch: diagonal block by eight flag-synchronised strips, rows below alongside ----
         FusedArgs fa;
@@ -2177,29 +2032,10 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
         fa.nbk = (int)nbk; fa.rows_below = (int)rem; fa.info = d_info; fa.pivot_base = (long)k0;
         fa.strideD = strideA; fa.strideL = strideL; fa.strideI = strideI;
         fa.status = d_status; fa.spin_limit = spin_limit;
-        fa.resident = nullptr; fa.wait_ptr = nullptr; fa.wait_target = 0; fa.sc1 = fused_sc1; fa.prog_sleep = fused_prog_sleep;
-        fa.g0 = 0;
-        if (!split) {
-          hipLaunchKernelGGL(fused_kernel, dim3((unsigned)((nbk + PB - 1) / PB + (rem + PB - 1) / PB), (unsigned)nbatch),
-                             dim3(256), FUSED_SMEM, P, fa);
-          DFH_LAUNCH_CHECK();
-        } else {
-          // Round 4: the eight diagonal strips and the strips of the rows below as TWO launches of the same kernel
-          // (the second with g0 = 8, on stream Q behind the larger part of the previous panel's look-ahead product):
-          // the diagonal chain of this panel then waits only for the 512 x 512 block it factors, not for the whole
-          // block column (rem x 512 x 512 at 24 TF/s in 64 x 64 tiles: 55 - 80 us of every panel of an n = 4096
-          // factorisation, tools/r4_run23.sh).  Both launches talk through the panel's flags as before; Q takes
-          // over everything P was made to wait for through e_copy.
-          DFH_HIP(hipEventRecord(e_copy, P));
-          hipLaunchKernelGGL(fused_kernel, dim3((unsigned)(NB / PB), 1), dim3(256), FUSED_SMEM, P, fa);
-          DFH_LAUNCH_CHECK();
-          DFH_HIP(hipStreamWaitEvent(Q, e_copy, 0));
-          fa.g0 = (int)(NB / PB);
-          hipLaunchKernelGGL(fused_kernel, dim3((unsigned)((rem + PB - 1) / PB), 1), dim3(256), FUSED_SMEM, Q, fa);
-          DFH_LAUNCH_CHECK();
-          DFH_HIP(hipEventRecord(e_diag, Q));
-          DFH_HIP(hipStreamWaitEvent(P, e_diag, 0));
-        }
+        fa.resident = nullptr; fa.wait_ptr = nullptr; fa.wait_target = 0; fa.prog_sleep = fused_prog_sleep;
+        hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)((nbk + PB - 1) / PB + (rem + PB - 1) / PB), (unsigned)nbatch),
+                           dim3(256), FUSED_SMEM, P, fa);
+        DFH_LAUNCH_CHECK();
       }
       // ---- 64-wide pivot steps: factor, solve every row below, update the rest of the panel ----
       for (int64_t j0 = 0; j0 < (fused ? 0 : nbk); j0 += PB) {
@@ -2239,18 +2075,7 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
         if (e_trail_prev) DFH_HIP(hipStreamWaitEvent(P, e_trail_prev, 0));
         const int64_t nb1 = rem < NB ? rem : NB;
         double* C1 = A + (k0 + nbk) * lda + (k0 + nbk);   // rows k+1.., block column k+1
-        if (!split || rem <= nb1) {
-          DFH_TRY(gemm_f64(ctx, 0, rem, nb1, kw, -1.0, A21, lda, A21, lda, 1.0, C1, lda, C1, lda, &bA));
-        } else {
-          // the next diagonal block on the chain's stream, the rows under it on Q (the next panel's rows-below
-          // launch follows them there)
-          DFH_TRY(gemm_f64(ctx, GEMM_LOWER, nb1, nb1, kw, -1.0, A21, lda, A21, lda, 1.0, C1, lda, C1, lda, &bA));
-          StreamSwap on_q(ctx, Q);
-          DFH_HIP(hipStreamWaitEvent(Q, e_panel, 0));
-          if (e_trail_prev) DFH_HIP(hipStreamWaitEvent(Q, e_trail_prev, 0));
-          DFH_TRY(gemm_f64(ctx, 0, rem - nb1, nb1, kw, -1.0, A21 + nb1 * lda, lda, A21, lda, 1.0, C1 + nb1 * lda, lda,
-                           C1 + nb1 * lda, lda, &bA));
-        }
+        DFH_TRY(gemm_f64(ctx, 0, rem, nb1, kw, -1.0, A21, lda, A21, lda, 1.0, C1, lda, C1, lda, &bA));
       }
     }
     DFH_TRY(aux_block(e_panel, X));
@@ -2267,16 +2092,7 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
       const double* A31 = A + (k0 + nbk + NB) * lda + (k0 + nbk - kw);   // rows k+2.. of the panel(s)
       double* A33 = A + (k0 + nbk + NB) * lda + (k0 + nbk + NB);
       DFH_HIP(hipStreamWaitEvent(M, e_panel, 0));
-      {
-        // DFH_CHOL_HALF_OCC=1: trailing update at one workgroup per CU, leaving slots for the
-        // latency-bound panel kernels of the look-ahead stream
-        static const bool half = []() { const char* e = getenv("DFH_CHOL_HALF_OCC"); return e && atoi(e) != 0; }();
-        const bool old = ctx->gemm_half_occupancy;
-        if (half) ctx->gemm_half_occupancy = true;
-        const int rc_t = gemm_f64(ctx, GEMM_LOWER, rem2, rem2, kw, -1.0, A31, lda, A31, lda, 1.0, A33, lda, A33, lda, &bA);
-        ctx->gemm_half_occupancy = old;
-        DFH_TRY(rc_t);
-      }
+      DFH_TRY(gemm_f64(ctx, GEMM_LOWER, rem2, rem2, kw, -1.0, A31, lda, A31, lda, 1.0, A33, lda, A33, lda, &bA));
       DFH_HIP(hipEventRecord(e_trail, M));
     } else {
       // nothing for M to do: keep the event chain well-formed for the next panel's wait
@@ -2935,9 +2751,7 @@ extern "C" int dfh_debug_panel_data(double* A_out, double* Lfac_out) {
 extern "C" int dfh_debug_panel_stamps(dfh_ctx* ctx, int reps, int rows_below, double* ms_out, long long* stamps_out) {
   DFH_ARG(ctx && reps > 0 && rows_below >= 0 && ms_out && stamps_out);
   DFH_HIP(hipSetDevice(ctx->device));
-  static const bool fused_tr = env_int("DFH_CHOL_FUSED_TR", 1) != 0;
-  void (*const fused_kernel)(FusedArgs) = fused_tr ? panel_fused_kernel<true> : panel_fused_kernel<false>;
-  DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_kernel),
+  DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_fused_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_SMEM));
   const int64_t nn = 512, rows = nn + rows_below;
   const int nwg = (int)(nn / PB + (rows_below + PB - 1) / PB);
@@ -2970,11 +2784,11 @@ extern "C" int dfh_debug_panel_stamps(dfh_ctx* ctx, int reps, int rows_below, do
     fa.nbk = (int)nn; fa.rows_below = rows_below; fa.info = d_info; fa.pivot_base = 0;
     fa.strideD = 0; fa.strideL = 0; fa.strideI = 0;
     fa.status = reinterpret_cast<unsigned long long*>(d_info + CHOL_MAX_BATCH + 8); fa.spin_limit = SPIN_LIMIT_DEFAULT;
-    fa.resident = nullptr; fa.wait_ptr = nullptr; fa.wait_target = 0; fa.sc1 = env_int("DFH_CHOL_FUSED_SC1", 1) != 0 ? 1 : 0;
-    fa.prog_sleep = env_int("DFH_CHOL_PROG_SLEEP", 8); fa.g0 = 0;
+    fa.resident = nullptr; fa.wait_ptr = nullptr; fa.wait_target = 0;
+    fa.prog_sleep = env_int("DFH_CHOL_PROG_SLEEP", 8);
     fa.stamps = d_st;
     DFH_HIP(hipEventRecord(e0, S));
-    hipLaunchKernelGGL(fused_kernel, dim3((unsigned)nwg, 1), dim3(256), FUSED_SMEM, S, fa);
+    hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)nwg, 1), dim3(256), FUSED_SMEM, S, fa);
     DFH_HIP(hipEventRecord(e1, S));
     DFH_HIP(hipStreamSynchronize(S));
     float ms = 0.f;

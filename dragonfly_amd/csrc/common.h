@@ -57,7 +57,6 @@ struct dfh_ctx {
   hipStream_t side = nullptr;        // high-priority panel stream of the look-ahead Cholesky
   hipStream_t bulk = nullptr;        // low-priority stream: next chunk's cross kernel + TRSM (TS)
   hipStream_t aux = nullptr;         // off-critical-path work of the factorisation (block inverses)
-  hipStream_t bulk_normal = nullptr; // normal-priority twin of `side` (experiments: DFH_CHOL_LR_NORMAL_PRIO)
   std::vector<hipEvent_t> evpool;    // untimed events for cross-stream ordering
   // factorisations that were repeated on the schedule without inter-workgroup hand-offs (a bounded wait
   // expired, or a block inverse was too poor for the resident panels) -- dfh_ctx_counters; after two in a row
@@ -83,10 +82,6 @@ struct dfh_ctx {
   char name[256] = {0};
   int n_cu = 256;
   double chunk_cap_gib = 0.0;        // posterior chunk cap of this context (api.hip: pick_chunk), set on first use
-  // per-launch HIP-event profile of the GEMM kernel (bench.py roofline numbers)
-  // When set, 128x128 GEMM launches request > 80 KB of LDS so that only ONE workgroup fits per
-  // CU: the other half of every CU stays available to latency-critical kernels of another stream.
-  bool gemm_half_occupancy = false;
   // The next symmetric single-part Gram matrix is wanted as its lower triangle only (tiles on and below the diagonal;
   // the rest of the buffer is left as it is): the fit path, whose factorisation reads nothing above the diagonal.
   bool km_lower_only = false;
@@ -95,6 +90,7 @@ struct dfh_ctx {
   // gemm_cond_thr) and the look-ahead tile order with its completion counters.
   const double* gemm_cond = nullptr; double gemm_cond_thr = 0.0;
   int* gemm_la_cnt = nullptr;
+  // per-launch HIP-event profile of the GEMM kernel (bench.py roofline numbers)
   bool gemm_prof = false;
   struct GemmRec { hipEvent_t e0, e1; double flops, bytes; int variant; };
   std::vector<GemmRec> gemm_recs;

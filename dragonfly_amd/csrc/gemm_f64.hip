@@ -404,15 +404,11 @@ int launch(dfh_ctx* ctx, const GemmArgs& p, dim3 grid, const GemmExt* x = nullpt
   const void* kern = !EXT ? reinterpret_cast<const void*>(gemm_f64_kernel<TRANSB, EDGE, WT>)
                           : (la ? reinterpret_cast<const void*>(gemm_f64_la_kernel<EDGE>)
                                 : reinterpret_cast<const void*>(gemm_f64_cond_kernel<EDGE>));
-  constexpr int HALF_OCC_SMEM = 84 * 1024;            // two of these do not fit in 160 KB
-  constexpr int MAX_SMEM = (WT == 4) ? HALF_OCC_SMEM : Geo<WT>::SMEM_BYTES;
+  constexpr int smem = Geo<WT>::SMEM_BYTES;
   if (!attr_set) {
-    DFH_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_SMEM));
+    DFH_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     attr_set = true;
   }
-  // Optional half occupancy (> 80 KB of LDS keeps a second workgroup off the CU): used for bulk
-  // GEMMs that run beside latency-critical kernels of another stream, which then find free slots.
-  const int smem = (WT == 4 && ctx->gemm_half_occupancy) ? HALF_OCC_SMEM : Geo<WT>::SMEM_BYTES;
   dfh_ctx::GemmRec* rec = nullptr;
   if (ctx->gemm_prof) {
     if (ctx->gemm_used == ctx->gemm_recs.size()) {
@@ -691,19 +687,6 @@ int gemm_f64(dfh_ctx* ctx, int flags, int64_t M, int64_t N, int64_t K, double al
   const long t128 = ((M + 127) / 128) * ((N + 127) / 128) * (long)count;
   if (use_ext) return dispatch<4>(ctx, p, count, edge, &ext);
   if (t128 < 192) return dispatch<2>(ctx, p, count, edge);
-  // Tuning knob (tools/gemm_rows.py): cut a tall product into launches of this many rows.  Measured
-  // on the posterior shape 262144 x 512 x 8192: L2 misses fall from 1.9x to 1.5x the operand bytes
-  // (two-wave launches keep the tiles that share a panel in step), the time does not move (31.55 vs
-  // 31.61 ms, 69.7 TF/s) -- the kernel is bound by the fp64 pipe, not by HBM.  Off by default.
-  static const long split_rows = getenv("DFH_GEMM_SPLIT_ROWS") ? atol(getenv("DFH_GEMM_SPLIT_ROWS")) : 0;
-  if (split_rows >= 128 && !batch && !(flags & GEMM_LOWER) && M > split_rows) {
-    for (int64_t r0 = 0; r0 < M; r0 += split_rows) {
-      const int64_t mr = (M - r0 < split_rows) ? M - r0 : split_rows;
-      p.M = (int)mr; p.A = A + r0 * lda; p.Cin = Cin ? Cin + r0 * ldcin : nullptr; p.Cout = Cout + r0 * ldc;
-      DFH_TRY(dispatch<4>(ctx, p, count, edge));
-    }
-    return DFH_OK;
-  }
   if (!edge && !(flags & GEMM_LOWER) && (N % 128) == 0 && (M % 128) != 0 && M >= 1024) {
     // A ragged last row tile would send EVERY tile through the bounds-checked kernel (scalar,
     // predicated operand loads): the full row tiles take the fast kernel, the < 128 leftover rows a

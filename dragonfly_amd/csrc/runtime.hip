@@ -71,7 +71,6 @@ extern "C" int dfh_ctx_create(int device, dfh_ctx** out) {
     DFH_HIP(hipStreamCreateWithPriority(&ctx->side, hipStreamNonBlocking, greatest));
     DFH_HIP(hipStreamCreateWithPriority(&ctx->bulk, hipStreamNonBlocking, least));
     DFH_HIP(hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
-    DFH_HIP(hipStreamCreateWithFlags(&ctx->bulk_normal, hipStreamNonBlocking));
   }
   DFH_HIP(hipEventCreate(&ctx->ev0));
   DFH_HIP(hipEventCreate(&ctx->ev1));
@@ -124,7 +123,6 @@ extern "C" void dfh_ctx_destroy(dfh_ctx* ctx) {
   if (ctx->side) (void)hipStreamDestroy(ctx->side);
   if (ctx->bulk) (void)hipStreamDestroy(ctx->bulk);
   if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
-  if (ctx->bulk_normal) (void)hipStreamDestroy(ctx->bulk_normal);
   (void)hipStreamDestroy(ctx->main_stream);
   delete ctx;
 }

@@ -1,8 +1,9 @@
 """MI355X: the factorisation's schedule variants -- trailing updates after every second panel
-(DFH_CHOL_PAIR), panel strips (DFH_CHOL_STRIPS), one launch per panel (DFH_CHOL_FUSED) -- are chosen by
-problem size and batch size; here each is forced on
-(and off) for small sizes too, in a subprocess (the switches are read once per process), so that
-every path sees ragged sizes, odd and even panel counts and lock-step batches."""
+(DFH_CHOL_PAIR), panel strips (DFH_CHOL_STRIPS), one launch per panel (DFH_CHOL_FUSED), the resident
+look-ahead (DFH_CHOL_LR) -- are chosen by problem size and batch size; here each is forced on (and off)
+for small sizes too, in a subprocess (the switches are read once per process), so that every path sees
+ragged sizes, odd and even panel counts and lock-step batches.  The hand-off time-out and its fallback
+without hand-offs (DFH_CHOL_SAFE) are forced the same way."""
 import os
 import subprocess
 import sys
@@ -34,13 +35,7 @@ VARIANTS = {
   'forced-handoff-timeout': {'DFH_TEST_SPIN_LIMIT': '0'},
   'forced-handoff-timeout+resident': {'DFH_TEST_SPIN_LIMIT': '0', 'DFH_CHOL_LR_MIN_REM': '640'},
   'no-handoffs': {'DFH_CHOL_SAFE': '1'},
-  # round 4: the one-launch panel in its round-3 form (strip rows in the accumulators' rows; fences or
-  # write-through hand-offs), and the transposed form in lock-step batches / with lazy polling
-  'fused-panels-round3-form': {'DFH_CHOL_FUSED_TR': '0', 'DFH_CHOL_FUSED_SC1': '0'},
-  'fused-panels-round3-form+write-through': {'DFH_CHOL_FUSED_TR': '0', 'DFH_CHOL_FUSED_SC1': '1'},
-  'fused-panels-round3-form-in-batches': {'DFH_CHOL_FUSED_TR': '0', 'DFH_CHOL_FUSED_MAX_BATCH': '64'},
-  'split-panels': {'DFH_CHOL_FUSED_SPLIT': '1'},
-  'split-panels+paired': {'DFH_CHOL_FUSED_SPLIT': '1', 'DFH_CHOL_PAIR_MIN_REM': '0'},
+  # round 4: the one-launch panel in lock-step batches with lazy polling
   'transposed-panels-lazy-polling': {'DFH_CHOL_PROG_SLEEP': '64', 'DFH_CHOL_FUSED_MAX_BATCH': '64'},
 }
 

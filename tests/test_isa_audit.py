@@ -1,6 +1,6 @@
 """The built library's machine code holds no register that is written and never read.
 
-That is the signature of the compiler fault behind the "scalar wave index" build of panel_fused_kernel<true>
+That is the signature of the compiler fault behind the "scalar wave index" build of panel_fused_kernel
 (docs/NOTES_r05.md section 2, profiles/r05_scalar_w_root_cause.txt): one dword of a spilled accumulator tuple
 parked in an AGPR and never put back.  It depends on the register allocation, not on the source, so it is checked
 on what was actually built -- here on CPU, with the ROCm LLVM tools.
@@ -102,12 +102,12 @@ def test_atomics_and_partly_used_tuples_are_not_findings():
 # scratch bytes per lane as recorded in profiles/r05_kernel_resource_usage.txt: the throughput kernels have none, the
 # latency-chain kernels of the factorisation must not get worse than what the round's timings were measured with
 _NO_SCRATCH = ('gemm_f64_kernel', 'lml_wg_kernel', 'kernmat_sym', 'kernmat_strip', 'trtri64_kernel', 'k_lml_tiny', 'k_pack_fused')
-_SCRATCH_CEILING = {'panel_fused_kernelILb1E': 388, 'panel_fused_kernelILb0E': 188, 'panel_strip_kernel': 228,
+_SCRATCH_CEILING = {'panel_fused_kernel': 388, 'panel_strip_kernel': 228,
                     'lml_team_kernel': 52, 'diag_step64_kernel': 48, 'gemm_f64_cond_kernel': 44, 'gemm_f64_la_kernel': 12}
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(isa_audit.LLVM, 'llvm-readelf')), reason='ROCm LLVM tools not found')
-def test_scratch_of_the_built_kernels_is_what_was_recorded():
+def test_scratch_of_the_built_kernels_is_within_the_recorded_ceilings():
   usage = isa_audit.resource_usage(LIB)
   assert len(usage) >= 80, 'only %d kernels found in the metadata' % len(usage)
   seen = set()

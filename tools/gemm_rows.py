@@ -1,5 +1,5 @@
 """Posterior-TRSM-shaped GEMM launches (M x 512 x K, C -= A.B^T): time per launch for one tree
-(DFH_ROOT) and one DFH_GEMM_SPLIT_ROWS setting.  Used with rocprofv3 --pmc FETCH_SIZE as well."""
+(DFH_ROOT).  Used with rocprofv3 --pmc FETCH_SIZE as well."""
 import os, sys
 root = os.environ.get('DFH_ROOT', os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, root)
@@ -25,6 +25,6 @@ for K in [int(k) for k in os.environ.get('KS', '4096,8192,16384').split(',')]:
   for _ in range(reps):
     eng.timer_begin(); run(); ts.append(eng.timer_end())
   ms = sorted(ts)[len(ts) // 2]
-  print('%s split=%s pad=%d  %d x %d x %d: %8.3f ms  %5.1f TF/s' % (os.path.basename(root), os.environ.get('DFH_GEMM_SPLIT_ROWS', '0'),
+  print('%s pad=%d  %d x %d x %d: %8.3f ms  %5.1f TF/s' % (os.path.basename(root),
         PAD, M, N, K, ms, 2.0 * M * N * K / (ms * 1e-3) / 1e12), flush=True)
   A.free(); B.free(); Cd.free()

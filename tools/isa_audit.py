@@ -2,7 +2,7 @@
 
     python tools/isa_audit.py [path/to/libdfhip.so | file.s ...]      (exit status 1 if anything is flagged)
 
-Why this exists (docs/NOTES_r05.md section 2): the "scalar wave index" build of panel_fused_kernel<true> that
+Why this exists (docs/NOTES_r05.md section 2): the "scalar wave index" build of panel_fused_kernel that
 produced NaN from column 4 on was a register-allocation fault of the compiler, not of the source or the
 hardware.  Under the kernel's register pressure (512 of 512) the allocator split the spill of one 8-dword
 accumulator tuple into  scratch_store_dwordx3 (dwords 0-2) + v_accvgpr_write a191 (dword 3, "Reload Reuse")
