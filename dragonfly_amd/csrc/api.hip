@@ -23,7 +23,9 @@ struct dfh_gp {
   double* alpha = nullptr;       // [n]
   bool upper_zeroed = false;
   bool gram = false;             // built from a host-evaluated Gram matrix: no kernel, no packed inputs
+  int psd_flags = 0;             // DFH_FIT_PROJECT_FIRST / DFH_FIT_TRY_BEFORE_PROJECT the fit ran under (L is not chol(K + noise I) of the kernel's K)
 };
+constexpr int DFH_FIT_PSD_FLAGS = DFH_FIT_PROJECT_FIRST | DFH_FIT_TRY_BEFORE_PROJECT;
 
 namespace {
 
@@ -276,6 +278,7 @@ int halluc_prepare(dfh_gp* gp, const double* Xh_user, int64_t q, Halluc* h) {
   if (q <= 0) return DFH_OK;
   DFH_ARG(q <= 4096);
   if (gp->diag_jitter != 0.0) return DFH_ERR_NOT_PD;
+  if (gp->psd_flags) return DFH_ERR_NOT_PD;      // the reference projects the whole augmented matrix (gp_core.py:199-206)
   const KernDev& kd = gp->kd;
   const double* Xh = nullptr;
   DFH_TRY(to_device(ctx, Xh_user, (size_t)q * gp->d * 8, SCR_STAGE_C, &Xh));
@@ -642,6 +645,44 @@ static int gp_alpha_and_lml(dfh_gp* gp, const double* dy, double* lml) {
   return DFH_OK;
 }
 
+// gp->L <- the factor of K + noise_var I for the n x n kernel matrix dK (device, without noise, left as it is) under
+// _get_cholesky_decomp's three branches (gp_core.py:827-847); shared by dfh_gp_fit_gram and the flagged dfh_gp_fit / dfh_gp_append
+static int factor_gram_psd(dfh_gp* gp, const double* dK, int flags, int32_t* jitter_power) {
+  dfh_ctx* ctx = gp->ctx;
+  const int64_t n = gp->n;
+  const double noise_var = gp->noise_var;
+  auto build_M = [&]() -> int {     // K + noise_var * I     (gp_core.py:843)
+    DFH_TRY(copy_matrix(ctx, dK, n, gp->L, n, n, n));
+    return add_diag(ctx, gp->L, n, n, noise_var);
+  };
+  bool project = (flags & DFH_FIT_PROJECT_FIRST) != 0;
+  if (flags & DFH_FIT_TRY_BEFORE_PROJECT) {
+    // gp_core.py:829-837: plain Cholesky of K + noise I (no ladder); only if that fails, project
+    DFH_TRY(build_M());
+    SectionTimer t(ctx, DFH_T_CHOL);
+    int64_t piv = 0;
+    const std::function<int()> rebuild_M = build_M;      // (a hand-off time-out repeats on the safe schedule)
+    const int rc = cholesky_device(ctx, gp->L, n, n, gp->inv, &piv, 1, 0, 0, gp->refine.data(), false, &rebuild_M);
+    if (rc == DFH_OK) return DFH_OK;
+    if (rc != DFH_ERR_NOT_PD) return rc;
+    project = true;
+  }
+  if (project) {
+    // gp_core.py:838-841: the kernel matrix (without noise) goes to the PSD cone first
+    double* Kp = nullptr;
+    DFH_TRY(scratch_get(ctx, SCR_TSK, (size_t)n * n * 8, (void**)&Kp));
+    DFH_TRY(psd_project_device(ctx, dK, n, n, 0.0, Kp, n));
+    dK = Kp;
+  }
+  DFH_TRY(build_M());
+  {
+    SectionTimer t(ctx, DFH_T_CHOL);
+    DFH_TRY(stable_cholesky_device(ctx, gp->L, n, gp->inv, !(flags & DFH_FIT_NO_JITTER), build_M,
+                                   jitter_power, &gp->diag_jitter, 0, gp->refine.data()));
+  }
+  return DFH_OK;
+}
+
 extern "C" int dfh_gp_fit(dfh_ctx* ctx, const dfh_kernel_desc* k, const double* X, int64_t n, int64_t d,
                           const double* y_centred, double noise_var, int flags, dfh_gp** out,
                           double* lml, int32_t* jitter_power) {
@@ -684,6 +725,19 @@ extern "C" int dfh_gp_fit(dfh_ctx* ctx, const dfh_kernel_desc* k, const double* 
     {
       SectionTimer t(ctx, DFH_T_KERNMAT);
       DFH_TRY(pack_scaled(ctx, kd, 0, kd.n_parts, false, dX, n, d, gp->Xp, gp->Np));
+    }
+    if (flags & DFH_FIT_PSD_FLAGS) {
+      // gp_core.py:827-841 from the descriptor: the whole kernel matrix (no noise, both triangles: the projection
+      // multiplies with it) is built in a workspace, and the factor comes from it as dfh_gp_fit_gram's does
+      gp->psd_flags = flags & DFH_FIT_PSD_FLAGS;
+      double* Kw = nullptr;
+      DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)n * n * 8, (void**)&Kw));
+      {
+        SectionTimer t(ctx, DFH_T_KERNMAT);
+        DFH_TRY(kernmat_packed(ctx, kd, 0, kd.n_parts, true, gp->Xp, gp->Np, n, gp->Xp, gp->Np, n, true, 0.0, Kw, n));
+      }
+      DFH_TRY(factor_gram_psd(gp, Kw, flags, jitter_power));
+      return gp_alpha_and_lml(gp, dy, lml);
     }
     DFH_TRY(build_M());
     {
@@ -729,35 +783,7 @@ extern "C" int dfh_gp_fit_gram(dfh_ctx* ctx, const double* K, int64_t n, const d
     const double *dK = nullptr, *dy = nullptr;
     DFH_TRY(to_device(ctx, K, (size_t)n * n * 8, SCR_KCT, &dK));
     DFH_TRY(to_device(ctx, y_centred, (size_t)n * 8, SCR_STAGE_B, &dy));
-    auto build_M = [&]() -> int {     // K + noise_var * I     (gp_core.py:843)
-      DFH_TRY(copy_matrix(ctx, dK, n, gp->L, n, n, n));
-      return add_diag(ctx, gp->L, n, n, noise_var);
-    };
-    bool project = (flags & DFH_FIT_PROJECT_FIRST) != 0;
-    if (flags & DFH_FIT_TRY_BEFORE_PROJECT) {
-      // gp_core.py:829-837: plain Cholesky of K + noise I (no ladder); only if that fails, project
-      DFH_TRY(build_M());
-      SectionTimer t(ctx, DFH_T_CHOL);
-      int64_t piv = 0;
-      const std::function<int()> rebuild_M = build_M;      // (a hand-off time-out repeats on the safe schedule)
-      const int rc = cholesky_device(ctx, gp->L, n, n, gp->inv, &piv, 1, 0, 0, gp->refine.data(), false, &rebuild_M);
-      if (rc == DFH_OK) return gp_alpha_and_lml(gp, dy, lml);
-      if (rc != DFH_ERR_NOT_PD) return rc;
-      project = true;
-    }
-    if (project) {
-      // gp_core.py:838-841: the kernel matrix (without noise) goes to the PSD cone first
-      double* Kp = nullptr;
-      DFH_TRY(scratch_get(ctx, SCR_TSK, (size_t)n * n * 8, (void**)&Kp));
-      DFH_TRY(psd_project_device(ctx, dK, n, n, 0.0, Kp, n));
-      dK = Kp;
-    }
-    DFH_TRY(build_M());
-    {
-      SectionTimer t(ctx, DFH_T_CHOL);
-      DFH_TRY(stable_cholesky_device(ctx, gp->L, n, gp->inv, !(flags & DFH_FIT_NO_JITTER), build_M,
-                                     jitter_power, &gp->diag_jitter, 0, gp->refine.data()));
-    }
+    DFH_TRY(factor_gram_psd(gp, dK, flags, jitter_power));
     return gp_alpha_and_lml(gp, dy, lml);
   };
   int rc = body();
@@ -894,6 +920,16 @@ extern "C" int dfh_gp_append(dfh_gp* gp, const double* Xnew, int64_t q, const do
       DFH_TRY(pack_scaled(ctx, kd, 0, parts, false, dXn, q, d, Xpn, Npn));
     }
     auto full_refit = [&]() -> int {             // what build_posterior does: K' + noise I, ladder
+      if (gp->psd_flags) {                       // ... or the projection branches, as the fit this handle came from
+        g2->psd_flags = gp->psd_flags;
+        double* Kw = nullptr;
+        DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)n2 * n2 * 8, (void**)&Kw));
+        {
+          SectionTimer t(ctx, DFH_T_KERNMAT);
+          DFH_TRY(kernmat_packed(ctx, kd, 0, parts, true, g2->Xp, g2->Np, n2, g2->Xp, g2->Np, n2, true, 0.0, Kw, n2));
+        }
+        return factor_gram_psd(g2, Kw, gp->psd_flags | (flags & DFH_FIT_NO_JITTER), jitter_power);
+      }
       auto build_M = [&]() -> int {
         SectionTimer t(ctx, DFH_T_KERNMAT);
         return kernmat_packed(ctx, kd, 0, parts, true, g2->Xp, g2->Np, n2, g2->Xp, g2->Np, n2, true,
@@ -905,7 +941,7 @@ extern "C" int dfh_gp_append(dfh_gp* gp, const double* Xnew, int64_t q, const do
                                     jitter_power, &g2->diag_jitter, 0, g2->refine.data());
     };
     bool appended = false;
-    if (gp->diag_jitter == 0.0) {
+    if (gp->diag_jitter == 0.0 && !gp->psd_flags) {       // (a projection is not a block-row update)
       double* Bm = g2->L + n * n2;               // rows n.., columns 0..n-1
       double* S = g2->L + n * n2 + n;            // the new diagonal block (ld n2)
       DFH_TRY(copy_matrix(ctx, gp->L, n, g2->L, n2, n, n));
@@ -1466,6 +1502,31 @@ extern "C" int dfh_gp_lml_batch(dfh_ctx* ctx, const dfh_kernel_desc* descs, int3
   const double* dX = nullptr;
   if (flags & DFH_LML_X_IS_DEVICE) dX = X;
   else DFH_TRY(to_device(ctx, X, (size_t)n * d * 8, SCR_STAGE_A, &dX));
+  if (flags & DFH_FIT_PSD_FLAGS) {
+    // a projection is per matrix (96 GEMM steps each, psdproj.hip): every candidate is a fit of its own, as the
+    // candidates that need the ladder are
+    std::vector<double> yh((size_t)n), yc((size_t)n);
+    if (!(flags & DFH_LML_Y_IS_HOST) && is_device_ptr(y)) {
+      DFH_HIP(hipMemcpyAsync(yh.data(), y, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+      DFH_HIP(hipStreamSynchronize(ctx->stream));
+    } else {
+      std::memcpy(yh.data(), y, (size_t)n * 8);
+    }
+    double* dXown = nullptr;       // (the fit stages y through the workspaces; X must not sit in one of them)
+    DFH_TRY(dev_alloc(ctx, (size_t)n * d * 8, (void**)&dXown));
+    int rc = DFH_OK;
+    if (hipMemcpyAsync(dXown, dX, (size_t)n * d * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) rc = DFH_ERR_HIP;
+    for (int c = 0; c < nb && rc == DFH_OK; ++c) {
+      const double mc = mean_consts ? mean_consts[c] : 0.0;
+      for (int64_t i = 0; i < n; ++i) yc[(size_t)i] = yh[(size_t)i] - mc;
+      dfh_gp* g = nullptr;
+      rc = dfh_gp_fit(ctx, &descs[c], dXown, n, d, yc.data(), noise_vars[c], flags & (DFH_FIT_PSD_FLAGS | DFH_FIT_NO_JITTER), &g,
+                      lml_out + c, jitter_powers ? jitter_powers + c : nullptr);
+      if (g) dfh_gp_free(g);
+    }
+    dev_release(ctx, dXown);
+    return rc;
+  }
   static const bool tiny_enabled = []() { const char* e = getenv("DFH_LML_TINY"); return e ? atoi(e) != 0 : true; }();
   if (tiny_enabled && n > TINY64_MAX_N && n <= 255 && nb <= 64) {
     // a handful of mid-sized candidates (a slice sampler's call at 64 <= n <= 128): Gram matrix, factorisation and

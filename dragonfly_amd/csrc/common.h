@@ -222,15 +222,16 @@ int gemm_skinny_nt(dfh_ctx* ctx, int64_t m, int64_t N, int64_t K, double alpha, 
 // row norms Np[n][n_parts] ((X**2).sum(axis=1), general_utils.py:66-67).
 #define DFH_KERNEL_DIST 3   // internal: clip(dist_sq) itself (dfh_dist_squared)
 struct PartDev {
-  int kind;        // DFH_KERNEL_SE | DFH_KERNEL_MATERN | DFH_KERNEL_DIST | DFH_KERNEL_POLY | DFH_KERNEL_EXPDECAY
+  int kind;        // DFH_KERNEL_SE | DFH_KERNEL_MATERN | DFH_KERNEL_DIST | DFH_KERNEL_POLY | DFH_KERNEL_EXPDECAY | DFH_KERNEL_HAMMING
   int poff;        // first packed column
   int kc;          // packed (padded to 4) column count
-  int p;           // Matern: int(nu) ; Poly: order ; ExpDecay: number of (real) columns
+  int p;           // Matern: int(nu) ; Poly: order ; ExpDecay / Hamming: number of (real) columns
   double scale_c;  // SE / Poly / ExpDecay: scale ; Matern: scale * norm_constant (kernel.py:298)
   double s8, s2;   // Matern: sqrt(8 nu), sqrt(2 nu)
   double gfac;     // Matern: Gamma(p+1)/Gamma(2p+1) ; ExpDecay: offset
   double coeff[8]; // Matern: (p+i)!/(i!(p-i)!) ; ExpDecay: powers
-  double k0;       // SE / Matern: k_part(x, x) (distance 0); unused for the non-stationary kinds
+  double k0;       // SE / Matern: k_part(x, x) (distance 0); Hamming: the sum of the weights (k(x, x) for every x);
+                   // unused for Poly / ExpDecay
   // A part of an ADDITIVE FACTOR of a product kernel (an AdditiveKernel among the kernels of a
   // CoordinateProductKernel: the multi-fidelity GP with an additive domain model, gp/euclidean_gp.py:696-707):
   // the factor's parts are adjacent; they are summed (0 + k_1 + k_2 ..., kernel.py:490-493), the sum is
@@ -241,6 +242,13 @@ struct PartDev {
 };
 constexpr int FM_IN = 4, FM_BEGIN = 1, FM_END = 2;
 constexpr int EXPDECAY_MAX_DIM = 8;
+constexpr int HAMMING_MAX_DIM = 32;    // one operand chunk of the kernel-matrix kernel (KM_KC); one level of NumPy's pairwise sum
+// where the weights of the Hamming columns sit in a kernel's device image (kernmat.hip: blob_layout), from its start
+__host__ __device__ inline size_t blob_hw_offset(int n_parts, int P) {
+  const size_t p = P ? P : 1;
+  const size_t a16 = 15;
+  return ((sizeof(PartDev) * (size_t)n_parts + a16) & ~a16) + ((8 * p + a16) & ~a16) + 2 * ((4 * p + a16) & ~a16);
+}
 struct KernDev {
   int kind = 0, dim = 0, n_parts = 0, P = 0;
   bool multi = false;          // additive: sum over parts then outer scale; product: scale * prod over parts
@@ -251,13 +259,16 @@ struct KernDev {
   std::vector<int> cols;       // [P] source column per packed column (-1 = padding)
   std::vector<int> lcols;      // [P] column index local to the part (for pre-gathered inputs)
   std::vector<double> bw;      // [P]
+  std::vector<double> hw;      // [P] Hamming parts: the column's weight (0 for every other column)
   PartDev* d_parts = nullptr;
   int* d_cols = nullptr;
   int* d_lcols = nullptr;
   double* d_bw = nullptr;
   void* d_blob = nullptr;      // the one device allocation behind the four pointers (owned if set)
   double kxx = 0.0;            // prior variance k(x,x) of a stationary kernel
-  bool stationary = true;      // false with a Poly / ExpDecay part: k(x,x) depends on x (prior_diag)
+  bool stationary = true;      // false with a Poly / ExpDecay / Hamming part: the SE / Matern-only kernels do not apply, and
+                               // k(x,x) comes from prior_diag (it depends on x for Poly / ExpDecay; a Hamming part's is its k0)
+  bool hamming = false;        // some part is a Hamming kernel: the kernel-matrix instances that know the compare (kernmat.hip)
   // ESP kernel (DFH_KERNEL_ESP): one SE / Matern part per column, combined by Newton-Girard into the
   // elementary symmetric polynomial of order esp_order, times outer_scale.  multi is set (several parts)
   // and product is not: every consumer of multi / product must test esp first.

@@ -1,5 +1,5 @@
 // Kernel evaluation on the device: exp / sqrt for the arguments a stationary kernel produces, one part's value from a
-// squared distance (kern_eval), the polynomial / exponential-decay parts, the combination rule of a product kernel with
+// squared distance (kern_eval), the polynomial / exponential-decay / Hamming parts, the combination rule of a product kernel with
 // additive factors, NumPy's pairwise row sum of squares.  Shared by kernmat.hip (the kernel-matrix kernels, the tuning
 // objective of small problems) and chol.hip (the one-workgroup tuning objective with its Gram matrix built in the same
 // launch).  Include inside the translation unit's anonymous namespace.
@@ -104,6 +104,84 @@ __device__ __forceinline__ double expdecay_eval(const PartDev& pd, const double*
   double r = pd.scale_c;
   for (int c = 0; c < pd.p; ++c) r *= 1.0 / pow(1.0 + (x[c] + y[c]), pd.coeff[c]);
   return r + pd.gfac;
+}
+
+// Hamming kernel from the points' category codes (kernel.py:436-457, general_utils.py:113-145): (np.equal(x, y) * w).sum(),
+// the terms added in NumPy's order -- left to right below 8 columns, the eight accumulators of its pairwise sum
+// from 8 columns on (n <= HAMMING_MAX_DIM: one level, as np_sumsq).  A term is w_c or 0: a compare and a select,
+// no multiplication.  One call serves the R x C entries a lane holds of one accumulator block: rows x + r * xs,
+// columns y + j * ys (LDS), so that a column of codes is read once for all of them and the weights (w: uniform,
+// scalar loads) once per column.
+template <int R, int C>
+__device__ __forceinline__ void hamming_term(double w, const double* x, int xs, const double* y, int ys, int c, double (&t)[R][C]) {
+  double a[R], b[C];
+#pragma unroll
+  for (int r = 0; r < R; ++r) a[r] = x[r * xs + c];
+#pragma unroll
+  for (int j = 0; j < C; ++j) b[j] = y[j * ys + c];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int j = 0; j < C; ++j) t[r][j] = (a[r] == b[j]) ? w : 0.0;
+}
+
+template <int R, int C>
+__device__ __forceinline__ void hamming_add(double (&s)[R][C], const double (&t)[R][C]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int j = 0; j < C; ++j) s[r][j] += t[r][j];
+}
+
+// accumulator `lane` of the pairwise sum: terms lane, lane + 8, ... below n8
+template <int R, int C>
+__device__ __forceinline__ void hamming_lane(const double* w, int n8, int lane, const double* x, int xs, const double* y, int ys,
+                                             double (&s)[R][C]) {
+  double t[R][C];
+  hamming_term<R, C>(w[lane], x, xs, y, ys, lane, s);
+#pragma nounroll
+  for (int c = lane + 8; c < n8; c += 8) {
+    hamming_term<R, C>(w[c], x, xs, y, ys, c, t);
+    hamming_add<R, C>(s, t);
+  }
+}
+
+template <int R, int C>
+__device__ __forceinline__ void hamming_eval(const double* w, int n, const double* x, int xs, const double* y, int ys,
+                                             double (&kv)[R][C]) {
+  double t[R][C];
+  int c = 0;
+  if (n < 8) {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int j = 0; j < C; ++j) kv[r][j] = 0.0;
+  } else {
+    const int n8 = n - (n % 8);
+    double u[R][C], v[R][C];
+    // ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7))
+    hamming_lane<R, C>(w, n8, 0, x, xs, y, ys, kv);
+    hamming_lane<R, C>(w, n8, 1, x, xs, y, ys, t);
+    hamming_add<R, C>(kv, t);
+    hamming_lane<R, C>(w, n8, 2, x, xs, y, ys, u);
+    hamming_lane<R, C>(w, n8, 3, x, xs, y, ys, t);
+    hamming_add<R, C>(u, t);
+    hamming_add<R, C>(kv, u);
+    hamming_lane<R, C>(w, n8, 4, x, xs, y, ys, v);
+    hamming_lane<R, C>(w, n8, 5, x, xs, y, ys, t);
+    hamming_add<R, C>(v, t);
+    hamming_lane<R, C>(w, n8, 6, x, xs, y, ys, u);
+    hamming_lane<R, C>(w, n8, 7, x, xs, y, ys, t);
+    hamming_add<R, C>(u, t);
+    hamming_add<R, C>(v, u);
+    hamming_add<R, C>(kv, v);
+    c = n8;
+  }
+#pragma nounroll
+  for (; c < n; ++c) {
+    hamming_term<R, C>(w[c], x, xs, y, ys, c, t);
+    hamming_add<R, C>(kv, t);
+  }
 }
 
 // One part's value into the running result of a product kernel whose factors may be sums of parts

@@ -60,8 +60,14 @@ struct KmArgs {
 constexpr int KM_MU_BLOCK = 512;
 // NS: the parts may be polynomial / exponential-decay kernels (an instance of its own: their pow()
 // calls cost the stationary multi-part kernel its registers).  NESTED (with NS): a product kernel
-// with additive factors.
-template <int TJ, bool MULTI, bool NS = false, bool NESTED = false>
+// with additive factors.  HAM (with MULTI): the parts may also be Hamming kernels (a product with a Hamming factor is
+// the reference's CartesianProductKernel, kernel.py:504-538) -- instances of their own again, so that the kernels of
+// every description without a Hamming part stay what they were.  A Hamming part is a code region of its own ahead of
+// the dot-product accumulators: compares and selects on its columns in the operand tiles, no MFMA and no exponential,
+// and the matrix is still one launch.  The instance without the polynomial / exponential-decay branches (NS false:
+// SE / Matern x Hamming, Hamming alone) has no scratch; the two with them carry the call frame of pow() as their twins
+// without Hamming do (profiles/cp_kernel_resource_usage.txt).
+template <int TJ, bool MULTI, bool NS = false, bool NESTED = false, bool HAM = false>
 __global__ __launch_bounds__(256, 2) void kernmat_kernel(KmArgs p) {
   constexpr int BN = 2 * TJ * 16;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -93,8 +99,55 @@ __global__ __launch_bounds__(256, 2) void kernmat_kernel(KmArgs p) {
       for (int j = 0; j < TJ; ++j) fsum[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
   }
 
+  // the Hamming columns' weights: a section of the kernel's device image (uniform scalar loads like the parts)
+  const double* hw = HAM ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(p.parts) + blob_hw_offset(p.n_parts_total, p.P))
+                         : nullptr;
   for (int part = p.part_lo; part < p.part_hi; ++part) {
     const PartDev& pd = p.parts[part];          // stays in global memory: uniform scalar loads
+    if (HAM && pd.kind == DFH_KERNEL_HAMMING) {      // (uniform)
+      // A region of its own, before the accumulators of the dot products exist: the part's columns (kc <= KM_KC: one
+      // chunk) go to the operand tiles as below, and sum_c w_c [x_c == y_c] is taken there for the TJ entries this
+      // lane holds of a row, a row at a time (the barrier), so that the temporaries stay a row's beside res.
+      const int kh = pd.kc >> 1;
+      __syncthreads();
+      for (int idx = tid; idx < KM_BM * kh; idx += 256) {
+        const int r = idx / kh, c2 = (idx - r * kh) * 2;
+        const long row = m0 + r;
+        double2_t v = (double2_t){0.0, 0.0};
+        if (row < p.n1) v = *reinterpret_cast<const double2_t*>(p.Xp1 + row * p.P + pd.poff + c2);
+        *reinterpret_cast<double2_t*>(As + r * KM_KP + c2) = v;
+      }
+      for (int idx = tid; idx < BN * kh; idx += 256) {
+        const int r = idx / kh, c2 = (idx - r * kh) * 2;
+        const long row = n0 + r;
+        double2_t v = (double2_t){0.0, 0.0};
+        if (row < p.n2) v = *reinterpret_cast<const double2_t*>(p.Xp2 + row * p.P + pd.poff + c2);
+        *reinterpret_cast<double2_t*>(Bs + r * KM_KP + c2) = v;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int lr = wm * 64 + i * 16 + l4 + 4 * r;
+          double hk[1][TJ];
+          hamming_eval<1, TJ>(hw + pd.poff, pd.p, As + lr * KM_KP, 0, Bs + (wn * TJ * 16 + l15) * KM_KP, 16 * KM_KP, hk);
+#pragma unroll
+          for (int j = 0; j < TJ; ++j) {
+            const double kv = hk[0][j];
+            if (NESTED) {
+              double rr = res[i][j][r], ff = fsum[i][j][r];
+              combine_nested(pd, kv, rr, ff);
+              res[i][j][r] = rr; fsum[i][j][r] = ff;
+            } else {
+              res[i][j][r] = p.product ? res[i][j][r] * kv : res[i][j][r] + kv;
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      continue;
+    }
     double4_t acc[4][TJ];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -902,6 +955,10 @@ int fill_part(PartDev& pd, int kind, double scale, double nu) {
     pd.scale_c = scale; pd.gfac = nu;
     return DFH_OK;
   }
+  if (kind == DFH_KERNEL_HAMMING) {            // the weights go to the image's hw section, their sum to k0 (make_part)
+    pd.scale_c = 1.0;
+    return DFH_OK;
+  }
   // Matern: kernel.py:242-253, 259-270
   double frac = fmod(nu, 1.0);
   if (!(frac == 0.5) || nu < 0.5) {
@@ -942,26 +999,29 @@ double part_value_at_zero(const PartDev& pd) {
   return 0.0;
 }
 
-// device image of a KernDev: [parts | bw | cols | lcols], each section 16-byte aligned
+// device image of a KernDev: [parts | bw | cols | lcols | hw], each section 16-byte aligned (hw: the weight of
+// every packed column of a Hamming part, 0 elsewhere; the kernels find it with blob_hw_offset)
 static size_t pad16(size_t x) { return (x + 15) & ~(size_t)15; }
-static void blob_layout(const KernDev& kd, size_t off[4], size_t* total) {
+static void blob_layout(const KernDev& kd, size_t off[5], size_t* total) {
   const size_t P = kd.P ? kd.P : 1;
   off[0] = 0;
   off[1] = off[0] + pad16(sizeof(PartDev) * kd.parts.size());
   off[2] = off[1] + pad16(sizeof(double) * P);
   off[3] = off[2] + pad16(sizeof(int) * P);
-  *total = off[3] + pad16(sizeof(int) * P);
+  off[4] = blob_hw_offset((int)kd.parts.size(), kd.P);
+  *total = off[4] + pad16(sizeof(double) * P);
 }
 static void blob_fill(const KernDev& kd, char* host) {
-  size_t off[4], total;
+  size_t off[5], total;
   blob_layout(kd, off, &total);
   std::memcpy(host + off[0], kd.parts.data(), sizeof(PartDev) * kd.parts.size());
   std::memcpy(host + off[1], kd.bw.data(), sizeof(double) * kd.P);
   std::memcpy(host + off[2], kd.cols.data(), sizeof(int) * kd.P);
   std::memcpy(host + off[3], kd.lcols.data(), sizeof(int) * kd.P);
+  std::memcpy(host + off[4], kd.hw.data(), sizeof(double) * kd.P);
 }
 static void blob_point(KernDev* kd, char* dev) {
-  size_t off[4], total;
+  size_t off[5], total;
   blob_layout(*kd, off, &total);
   kd->d_parts = reinterpret_cast<PartDev*>(dev + off[0]);
   kd->d_bw = reinterpret_cast<double*>(dev + off[1]);
@@ -970,7 +1030,7 @@ static void blob_point(KernDev* kd, char* dev) {
 }
 
 int upload(dfh_ctx* ctx, KernDev* kd) {
-  size_t off[4], total;
+  size_t off[5], total;
   blob_layout(*kd, off, &total);
   std::vector<char> host(total, 0);
   blob_fill(*kd, host.data());
@@ -988,6 +1048,7 @@ void add_part_cols(KernDev* kd, PartDev& pd, const int* cols, const double* bw, 
     kd->cols.push_back(c < ncols ? cols[c] : -1);
     kd->lcols.push_back(c < ncols ? c : -1);
     kd->bw.push_back(c < ncols ? bw[c] : 1.0);
+    kd->hw.push_back(0.0);
   }
   kd->P += pd.kc;
 }
@@ -1520,6 +1581,23 @@ int lml_tiny_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double* dX
   return DFH_OK;
 }
 
+// (eq * wts).sum(axis=1) of a row whose entries all compare equal: NumPy's pairwise order (hamming_eval on the device)
+static double np_sum_host(const double* a, int n) {
+  if (n < 8) {
+    double res = 0.0;
+    for (int i = 0; i < n; ++i) res += a[i];
+    return res;
+  }
+  double r[8];
+  for (int j = 0; j < 8; ++j) r[j] = a[j];
+  int i = 8;
+  for (; i < n - (n % 8); i += 8)
+    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += a[i];
+  return res;
+}
+
 // One part from (kind, scale, nu, per-column parameters): SE / Matern bandwidths divide the inputs,
 // polynomial scalings multiply them (stored negated, see k_pack_cols), exponential-decay powers go
 // into the part and its inputs stay as they are.
@@ -1540,10 +1618,24 @@ static int make_part(KernDev* kd, int kind, double scale, double nu, const int* 
     }
     pd.p = ncols;
     for (int c = 0; c < ncols; ++c) { pd.coeff[c] = par[c]; bw[c] = 1.0; }
+  } else if (kind == DFH_KERNEL_HAMMING) {
+    if (ncols > HAMMING_MAX_DIM) {
+      dfh_set_error("Hamming kernel: at most %d dimensions (got %d)", HAMMING_MAX_DIM, ncols);
+      return DFH_ERR_BAD_ARG;
+    }
+    if (scale != 1.0 || nu != 0.0) {
+      dfh_set_error("Hamming kernel: scale must be 1 and nu 0 (got %g, %g)", scale, nu);
+      return DFH_ERR_BAD_ARG;
+    }
+    pd.p = ncols;
+    for (int c = 0; c < ncols; ++c) bw[c] = 1.0;         // the category codes stay as they are (x / 1.0)
+    pd.k0 = np_sum_host(par, ncols);                      // k(x, x) = sum_c w_c whatever x
   } else {
     for (int c = 0; c < ncols; ++c) bw[c] = par[c];
   }
   add_part_cols(kd, pd, cols, bw.data(), ncols);
+  if (kind == DFH_KERNEL_HAMMING)
+    for (int c = 0; c < ncols; ++c) kd->hw[(size_t)pd.poff + c] = par[c];
   kd->parts.push_back(pd);
   return DFH_OK;
 }
@@ -1554,9 +1646,9 @@ int kerndev_build_host(const dfh_kernel_desc* k, KernDev* kd) {
   DFH_ARG(k != nullptr && kd != nullptr);
   DFH_ARG(k->dim >= 1);
   kd->kind = k->kind; kd->dim = k->dim; kd->P = 0;
-  kd->parts.clear(); kd->cols.clear(); kd->lcols.clear(); kd->bw.clear();
+  kd->parts.clear(); kd->cols.clear(); kd->lcols.clear(); kd->bw.clear(); kd->hw.clear();
   kd->stationary = true; kd->kxx = 0.0;
-  kd->esp = false; kd->esp_order = 0;
+  kd->esp = false; kd->esp_order = 0; kd->hamming = false;
   if (k->kind == DFH_KERNEL_SE || k->kind == DFH_KERNEL_MATERN) {
     DFH_ARG(k->bw != nullptr);
     std::vector<int> ident(k->dim);
@@ -1564,10 +1656,11 @@ int kerndev_build_host(const dfh_kernel_desc* k, KernDev* kd) {
     DFH_TRY(make_part(kd, k->kind, k->scale, k->nu, ident.data(), k->bw, k->dim));
     kd->multi = false; kd->product = false; kd->outer_scale = 1.0; kd->nested = false;
     kd->kxx = kd->parts[0].k0;
-  } else if (k->kind == DFH_KERNEL_POLY || k->kind == DFH_KERNEL_EXPDECAY) {
+  } else if (k->kind == DFH_KERNEL_POLY || k->kind == DFH_KERNEL_EXPDECAY || k->kind == DFH_KERNEL_HAMMING) {
     // a product with one factor and outer scale 1 (1.0 * k is exact): the generic multi-part
     // kernel-matrix kernel is the only one that knows these kinds
     DFH_ARG(k->bw != nullptr);
+    kd->hamming = k->kind == DFH_KERNEL_HAMMING;
     std::vector<int> ident(k->dim);
     for (int i = 0; i < k->dim; ++i) ident[i] = i;
     DFH_TRY(make_part(kd, k->kind, k->scale, k->nu, ident.data(), k->bw, k->dim));
@@ -1587,7 +1680,8 @@ int kerndev_build_host(const dfh_kernel_desc* k, KernDev* kd) {
       for (int c = lo; c < hi; ++c) DFH_ARG(k->group_dims[c] >= 0 && k->group_dims[c] < k->dim);
       const int sk = k->sub_kind[g];
       // polynomial groups also in an additive kernel (the reference's factory builds them: euclidean_gp.py:870-879)
-      DFH_ARG(kind_is_stationary(sk) || sk == DFH_KERNEL_POLY || (product && sk == DFH_KERNEL_EXPDECAY));
+      DFH_ARG(kind_is_stationary(sk) || sk == DFH_KERNEL_POLY || (product && (sk == DFH_KERNEL_EXPDECAY || sk == DFH_KERNEL_HAMMING)));
+      if (sk == DFH_KERNEL_HAMMING) kd->hamming = true;
       DFH_TRY(make_part(kd, sk, k->sub_scale[g], k->sub_nu ? k->sub_nu[g] : 0.0, k->group_dims + lo,
                         k->sub_bw + lo, hi - lo));
       if (!kind_is_stationary(sk)) kd->stationary = false;
@@ -1600,7 +1694,7 @@ int kerndev_build_host(const dfh_kernel_desc* k, KernDev* kd) {
         const bool first = g == 0 || k->group_factor[g - 1] != f;
         const bool last = g + 1 == k->n_groups || k->group_factor[g + 1] != f;
         if (k->factor_is_sum[f]) {
-          DFH_ARG(sk != DFH_KERNEL_EXPDECAY);       // an additive kernel's groups: SE / Matern / polynomial
+          DFH_ARG(sk != DFH_KERNEL_EXPDECAY && sk != DFH_KERNEL_HAMMING);       // an additive kernel's groups: SE / Matern / polynomial
           pd.fmode = FM_IN | (first ? FM_BEGIN : 0) | (last ? FM_END : 0);
           pd.fscale = k->factor_scale[f];
           facc = first ? 0.0 + k0 : facc + k0;
@@ -1736,7 +1830,7 @@ int kerndev_build(dfh_ctx* ctx, const dfh_kernel_desc* k, KernDev* kd) {
 }
 
 size_t kerndev_blob_bytes(const KernDev& kd) {
-  size_t off[4], total;
+  size_t off[5], total;
   blob_layout(kd, off, &total);
   return total;
 }
@@ -1777,7 +1871,7 @@ int kerndev_upload_many(dfh_ctx* ctx, KernDev* kds, int count, void* d_blob, siz
 int kerndev_build_dist(dfh_ctx* ctx, int dim, KernDev* kd) {
   DFH_ARG(dim >= 1);
   kd->kind = DFH_KERNEL_DIST; kd->dim = dim; kd->P = 0;
-  kd->parts.clear(); kd->cols.clear(); kd->lcols.clear(); kd->bw.clear();
+  kd->parts.clear(); kd->cols.clear(); kd->lcols.clear(); kd->bw.clear(); kd->hw.clear();
   PartDev pd;
   DFH_TRY(fill_part(pd, DFH_KERNEL_DIST, 1.0, 0.0));
   std::vector<int> ident(dim);
@@ -1786,7 +1880,7 @@ int kerndev_build_dist(dfh_ctx* ctx, int dim, KernDev* kd) {
   add_part_cols(kd, pd, ident.data(), ones.data(), dim);
   kd->parts.push_back(pd);
   kd->multi = false; kd->outer_scale = 1.0; kd->kxx = 0.0;
-  kd->esp = false; kd->esp_order = 0;
+  kd->esp = false; kd->esp_order = 0; kd->hamming = false;
   kd->n_parts = 1;
   return upload(ctx, kd);
 }
@@ -2083,6 +2177,12 @@ int kernmat_packed(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bo
                                 hipFuncAttributeMaxDynamicSharedMemorySize, SM2));
     DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernmat_kernel<2, true, true, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, SM2));
+    DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernmat_kernel<2, true, false, false, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, SM2));
+    DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernmat_kernel<2, true, true, false, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, SM2));
+    DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernmat_kernel<2, true, true, true, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, SM2));
     attr_set = true;
   }
   if (!multi && part_hi == part_lo + 1 && (ldk & 1) == 0 && (reinterpret_cast<uintptr_t>(K) & 15) == 0 &&
@@ -2158,6 +2258,8 @@ int kernmat_packed(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bo
       return DFH_OK;
     }
   }
+  bool ham_pow = false;       // a Hamming part next to a polynomial / exponential-decay one: the instance with their pow()
+  for (const PartDev& pd : kd.parts) ham_pow = ham_pow || pd.kind == DFH_KERNEL_POLY || pd.kind == DFH_KERNEL_EXPDECAY;
   const int64_t rows_per_launch = 65535LL * KM_BM;
   for (int64_t r0 = 0; r0 < n1; r0 += rows_per_launch) {
     const int64_t rr = n1 - r0 < rows_per_launch ? n1 - r0 : rows_per_launch;
@@ -2166,7 +2268,10 @@ int kernmat_packed(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bo
     if (r0 != 0) b.symmetric = 0;    // only reachable for n1 > 8M rows; diagonal handled in slab 0
     if (multi) {
       dim3 grid((unsigned)((n2 + 63) / 64), (unsigned)((rr + KM_BM - 1) / KM_BM));
-      if (kd.nested) hipLaunchKernelGGL((kernmat_kernel<2, true, true, true>), grid, dim3(256), SM2, ctx->stream, b);
+      if (kd.hamming && kd.nested) hipLaunchKernelGGL((kernmat_kernel<2, true, true, true, true>), grid, dim3(256), SM2, ctx->stream, b);
+      else if (kd.hamming && ham_pow) hipLaunchKernelGGL((kernmat_kernel<2, true, true, false, true>), grid, dim3(256), SM2, ctx->stream, b);
+      else if (kd.hamming) hipLaunchKernelGGL((kernmat_kernel<2, true, false, false, true>), grid, dim3(256), SM2, ctx->stream, b);
+      else if (kd.nested) hipLaunchKernelGGL((kernmat_kernel<2, true, true, true>), grid, dim3(256), SM2, ctx->stream, b);
       else if (kd.stationary) hipLaunchKernelGGL((kernmat_kernel<2, true>), grid, dim3(256), SM2, ctx->stream, b);
       else hipLaunchKernelGGL((kernmat_kernel<2, true, true>), grid, dim3(256), SM2, ctx->stream, b);
     } else {

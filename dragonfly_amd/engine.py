@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ACQ_EI, ACQ_MEAN, ACQ_PI, ACQ_STD, ACQ_TTEI, ACQ_UCB, GET_ALPHA, GET_K, GET_L,
-                   INT32_MIN, KERNEL_ADDITIVE, KERNEL_ESP, KERNEL_EXPDECAY, KERNEL_MATERN, KERNEL_POLY, KERNEL_PRODUCT, KERNEL_SE,
+                   INT32_MIN, KERNEL_ADDITIVE, KERNEL_ESP, KERNEL_EXPDECAY, KERNEL_HAMMING, KERNEL_MATERN, KERNEL_POLY, KERNEL_PRODUCT, KERNEL_SE,
                    KernelDesc,
                    check)
 
@@ -99,7 +99,16 @@ class DeviceArray(object):
       pass
 
 
-_SINGLE_KINDS = {'se': KERNEL_SE, 'matern': KERNEL_MATERN, 'poly': KERNEL_POLY, 'expdecay': KERNEL_EXPDECAY}
+_SINGLE_KINDS = {'se': KERNEL_SE, 'matern': KERNEL_MATERN, 'poly': KERNEL_POLY, 'expdecay': KERNEL_EXPDECAY,
+                 'hamming': KERNEL_HAMMING}
+_PSD_FLAGS = {'guaranteed_psd': 0, 'project_first': _lib.FIT_PROJECT_FIRST, 'try_before_project': _lib.FIT_TRY_BEFORE_PROJECT}
+
+
+def _psd_flags(handle_non_psd_kernels):
+  """ The fit flag of one of _get_cholesky_decomp's branches (gp_core.py:827-847). """
+  if handle_non_psd_kernels not in _PSD_FLAGS:
+    raise ValueError('Unknown option for handle_non_psd_kernels: %s' % (handle_non_psd_kernels))
+  return _PSD_FLAGS[handle_non_psd_kernels]
 
 
 _DESC_DTYPE = np.dtype({'names': [f[0] for f in KernelDesc._fields_],
@@ -138,8 +147,10 @@ def _single_kind_descs(specs, d, backing):
 class KernelSpec(object):
   """ Host-side description of a Euclidean kernel, convertible to struct dfh_kernel_desc.
       kind: 'se' | 'matern' | 'poly' (nu = order, bandwidths = dim_scalings) | 'expdecay' (nu =
-      offset, bandwidths = powers) | 'additive' | 'product' (coordinate-wise product, kernel.py:541;
-      its factors may be any of the four single kinds, an additive kernel's se / matern / poly).
+      offset, bandwidths = powers) | 'hamming' (HammingKernel, kernel.py:436-457: bandwidths = dim_weights,
+      scale 1, nu 0; the columns hold category codes) | 'additive' | 'product' (coordinate-wise product,
+      kernel.py:541; its factors may be any of the five single kinds, an additive kernel's se / matern /
+      poly -- with a hamming factor it is the reference's CartesianProductKernel, kernel.py:504-538).
       A product may hold ADDITIVE FACTORS (an AdditiveKernel among its kernels): list the factor's
       groups like any others and give group_factors[g] = index of the factor group g belongs to
       (non-decreasing), factor_sums[f] = True for an additive factor, factor_scales[f] = its scale.
@@ -240,6 +251,7 @@ class KernelSpec(object):
 
 class Engine(object):
   """ One MI355X: a dfh_ctx (stream + workspaces). """
+  kernel_kinds = frozenset(_SINGLE_KINDS) | frozenset(['additive', 'product', 'esp'])     # what kernel_matrix / gp_fit describe
 
   def __init__(self, device=None):
     self.lib = _lib.load()
@@ -488,10 +500,13 @@ class Engine(object):
     return x
 
   # -- GP ----------------------------------------------------------------------------------
-  def gp_lml_batch(self, specs, X, y, mean_consts, noise_vars, allow_jitter=True, return_powers=False):
+  def gp_lml_batch(self, specs, X, y, mean_consts, noise_vars, allow_jitter=True, return_powers=False,
+                   handle_non_psd_kernels='guaranteed_psd'):
     """ Log marginal likelihoods of len(specs) hyper-parameter candidates on the same (X, y): the
         tuning objective of GPFitter (gp_core.py:551-564) for a list of candidates, fitted in
-        lock-step groups on the device.  y holds raw labels; mean_consts[c] is subtracted. """
+        lock-step groups on the device.  y holds raw labels; mean_consts[c] is subtracted.
+        handle_non_psd_kernels other than 'guaranteed_psd': every candidate's Gram matrix takes that
+        branch of _get_cholesky_decomp (gp_core.py:827-841), one candidate at a time. """
     nb = len(specs)
     Xh = X if isinstance(X, DeviceArray) else _f64(X)
     yh = y if isinstance(y, DeviceArray) else _f64(y)
@@ -510,7 +525,7 @@ class Engine(object):
       raise ValueError('gp_lml_batch: need one mean constant and one noise variance per candidate.')
     lml = np.empty(nb, dtype=np.float64)
     jps = np.empty(nb, dtype=np.int32)
-    flags = 0 if allow_jitter else _lib.FIT_NO_JITTER
+    flags = (0 if allow_jitter else _lib.FIT_NO_JITTER) | _psd_flags(handle_non_psd_kernels)
     if isinstance(Xh, DeviceArray):
       flags |= _lib.LML_X_IS_DEVICE
     if not isinstance(yh, DeviceArray):
@@ -538,15 +553,16 @@ class Engine(object):
     check(self.lib.dfh_project_psd(self.ctx, _ptr(M), n, float(epsilon), _ptr(out)))
     return out
 
-  def gp_fit(self, spec, X, y_centred, noise_var, allow_jitter=True):
-    """ Returns a FittedGP (posterior resident in HBM). """
-    return FittedGP(self, spec, X, y_centred, noise_var, allow_jitter)
+  def gp_fit(self, spec, X, y_centred, noise_var, allow_jitter=True, handle_non_psd_kernels='guaranteed_psd'):
+    """ Returns a FittedGP (posterior resident in HBM).  handle_non_psd_kernels as in gp_fit_gram: the Gram
+        matrix is built on the device from the descriptor and projected there. """
+    return FittedGP(self, spec, X, y_centred, noise_var, allow_jitter, handle_non_psd_kernels)
 
 
 class FittedGP(object):
   """ Handle of a dfh_gp: K, L, alpha live on the device. """
 
-  def __init__(self, engine, spec, X, y_centred, noise_var, allow_jitter=True):
+  def __init__(self, engine, spec, X, y_centred, noise_var, allow_jitter=True, handle_non_psd_kernels='guaranteed_psd'):
     self.engine = engine
     self.handle = None
     self.spec = spec
@@ -559,7 +575,8 @@ class FittedGP(object):
     lml = C.c_double(0)
     jp = C.c_int32(INT32_MIN)
     check(engine.lib.dfh_gp_fit(engine.ctx, C.byref(desc), _ptr(Xh), n, d, _ptr(yh),
-                                float(noise_var), 0 if allow_jitter else _lib.FIT_NO_JITTER,
+                                float(noise_var),
+                                (0 if allow_jitter else _lib.FIT_NO_JITTER) | _psd_flags(handle_non_psd_kernels),
                                 C.byref(h), C.byref(lml), C.byref(jp)))
     self.handle = h
     self.lml = lml.value
@@ -577,11 +594,7 @@ class FittedGP(object):
     h = C.c_void_p()
     lml = C.c_double(0)
     jp = C.c_int32(INT32_MIN)
-    if handle_non_psd_kernels not in ('guaranteed_psd', 'project_first', 'try_before_project'):
-      raise ValueError('Unknown option for handle_non_psd_kernels: %s' % (handle_non_psd_kernels))
-    flags = (0 if allow_jitter else _lib.FIT_NO_JITTER) | \
-        {'guaranteed_psd': 0, 'project_first': _lib.FIT_PROJECT_FIRST,
-         'try_before_project': _lib.FIT_TRY_BEFORE_PROJECT}[handle_non_psd_kernels]
+    flags = (0 if allow_jitter else _lib.FIT_NO_JITTER) | _psd_flags(handle_non_psd_kernels)
     check(engine.lib.dfh_gp_fit_gram(engine.ctx, _ptr(Kh), n, _ptr(yh), float(noise_var), flags, C.byref(h),
                                      C.byref(lml), C.byref(jp)))
     new = cls.__new__(cls)

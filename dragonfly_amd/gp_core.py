@@ -121,7 +121,7 @@ class GP(object):
       if fitted is not None and len(X_new) > 0 and fitted.n == n_old and self.incremental_updates \
          and not self._generic and fit_sig == self._posterior_signature(fitted.d):
         Y_centred = np.asarray(self.Y, dtype=np.float64) - self.mean_func(self.X)
-        self._fitted = fitted.append(_as_2d_array(X_new), Y_centred)
+        self._fitted = fitted.append(self._points_array(X_new), Y_centred)
         self._fit_sig = fit_sig
       else:
         self.build_posterior()
@@ -138,7 +138,18 @@ class GP(object):
     return self.kernel(self.X, self.X)
 
   def _X_array(self):
-    return _as_2d_array(self.X)
+    return self._points_array(self.X)
+
+  def _points_array(self, X):
+    """ Points as the dense matrix the kernel's descriptor speaks about (a GP on a Cartesian-product domain packs
+        its list-of-lists points here, cartesian_product_gp.py). """
+    return _as_2d_array(X)
+
+  def _fit_kwargs(self):
+    """ 'project_first' / 'try_before_project' travel to the device fit as flags (gp_core.py:827-841). """
+    if self.handle_non_psd_kernels == 'guaranteed_psd':
+      return {}
+    return {'handle_non_psd_kernels': self.handle_non_psd_kernels}
 
   def build_posterior(self):
     """ gp_core.py:155-163: K, L = chol(K + noise I), alpha -- one device call. """
@@ -157,12 +168,12 @@ class GP(object):
     X = hint if (hint is not None and hint.shape[0] == self.num_tr_data) else self._X_array()
     Y_centred = np.asarray(self.Y, dtype=np.float64) - self.mean_func(self.X)
     spec = self.kernel.to_spec(in_dim=X.shape[1])
-    self._fitted = get_engine().gp_fit(spec, X, Y_centred, self.noise_var)
+    self._fitted = get_engine().gp_fit(spec, X, Y_centred, self.noise_var, **self._fit_kwargs())
     self._fit_sig = self._posterior_signature(X.shape[1])
 
   def _posterior_signature(self, in_dim):
     """ What the cached factor depends on besides the data: kernel and noise variance. """
-    return (self.kernel.to_spec(in_dim=in_dim).signature(), float(self.noise_var))
+    return (self.kernel.to_spec(in_dim=in_dim).signature(), float(self.noise_var), self.handle_non_psd_kernels)
 
   def _need_fit(self):
     if self._fitted is None and self.num_tr_data > 0:
@@ -206,7 +217,7 @@ class GP(object):
     if uncert_form not in ('none', 'std', 'covar'):
       raise ValueError('uncert_form should be none, covar or std.')
     test_mean = self.mean_func(X_test)
-    Xt = X_test if self._generic else _as_2d_array(X_test)   # a caller-evaluated kernel takes any objects
+    Xt = X_test if self._generic else self._points_array(X_test)   # a caller-evaluated kernel takes any objects
     if self.num_tr_data == 0:
       # no data: the posterior is the prior (K_tetr is n_test x 0 in the reference)
       pred_mean = test_mean + np.zeros(len(Xt))
@@ -247,8 +258,8 @@ class GP(object):
     fitted = self._need_fit()
     if self._generic:
       return (pred_mean, self._generic_hallucinated_uncert(X_test, X_halluc, uncert_form))
-    Xt = _as_2d_array(X_test)
-    Xh = _as_2d_array(X_halluc)
+    Xt = self._points_array(X_test)
+    Xh = self._points_array(X_halluc)
     if uncert_form == 'covar':
       _, covar = fitted.predict_covar(Xt, X_halluc=Xh)
       return (pred_mean, covar)
@@ -311,7 +322,7 @@ class GP(object):
         the global np.random state exactly as draw_gaussian_samples' np.random.normal call does
         (Engine.random_normals: generated on the device, bit for bit). """
     if X_test is not None and num_samples == 1 and self.num_tr_data > 0 and not self._generic:
-      Xt = _as_2d_array(X_test)
+      Xt = self._points_array(X_test)
       test_mean = self.mean_func(X_test)
       fit = self._need_fit()
       draw = getattr(fit.engine, 'random_normals', None)      # the stand-in engine of the CPU tests has none

@@ -25,11 +25,16 @@ edited):
                __init__ calls super(EuclideanMFGP, self)).
   S2'' CP GP   (only with install(cartesian_product=True)) dragonfly.gp.cartesian_product_gp.CPGP ->
                dragonfly_amd.cartesian_product_gp.device_cpgp_class(...): the reference's own class body over the
-               device GP; the kernel (the reference's
-               CartesianProductKernel) stays on the host, the 'project_first' eigen-projection of
-               the Gram matrix and of every posterior covariance (gp_core.py:838-841, 849-857), the
-               factorisation and the posterior run on the device.  The CP fitter constructs its GP
-               through this module global.  Opt-in for the same reason as the MF GP.
+               device GP, and HammingKernel / CartesianProductKernel in dragonfly.gp.kernel and
+               dragonfly.gp.cartesian_product_gp -> our mirrors.  A CP kernel whose parts are SE, Matern,
+               exponential-decay or Hamming kernels is evaluated on the device from one product descriptor
+               (categories packed as codes), projected ('project_first', gp_core.py:838-841), factored and
+               evaluated there; with any other part (neural-network kernels, pre-computed distances) the
+               kernel stays on the host and only the projection, the factorisation and the posterior run
+               on the device.  The CP fitter constructs its GP through this module global.  Opt-in for
+               the same reason as the MF GP.  With batched_tuning, dragonfly.opt.gp_bandit.CPGPFitter and
+               dragonfly.opt.multiobjective_gp_bandit.CPGPFitter -> make_batched_cp_fitter(...): the S3 fitter's
+               batch objective for CP candidates, one dfh_gp_lml_batch call with the projection flag.
   S4 acquisitions  dispatchers are written into the namespaces
                dragonfly.opt.gpb_acquisitions.asy / syn / seq (looked up with getattr at
                dragonfly/opt/gp_bandit.py:490,510,651,681): the fused callables on Euclidean
@@ -85,6 +90,11 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False):
     import dragonfly.gp.cartesian_product_gp as ref_cpgp
     from . import cartesian_product_gp
     _set(ref_cpgp, 'CPGP', cartesian_product_gp.device_cpgp_class(ref_cpgp))
+    # the CP kernel factory builds its Hamming parts and the product itself by these two names, looked up at call time
+    # in both modules (cartesian_product_gp.py:19); the Euclidean parts already arrive as our mirrors
+    for name in ('HammingKernel', 'CartesianProductKernel'):
+      _set(ref_kernel, name, getattr(kernel, name))
+      _set(ref_cpgp, name, getattr(kernel, name))
   for ns_name in ('asy', 'syn', 'seq'):
     ref_ns = getattr(ref_acq, ns_name)
     our_ns = getattr(gpb_acquisitions, ns_name)
@@ -109,6 +119,12 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False):
     batched = make_batched_fitter(ref_egp.EuclideanGPFitter)
     _set(ref_gp_bandit, 'EuclideanGPFitter', batched)
     _set(ref_moo_bandit, 'EuclideanGPFitter', batched)
+    if cartesian_product:
+      # the names the CP bandits construct their fitter by (gp_bandit.py, multiobjective_gp_bandit.py)
+      import dragonfly.gp.cartesian_product_gp as ref_cpgp
+      batched_cp = make_batched_cp_fitter(ref_cpgp.CPGPFitter)
+      _set(ref_gp_bandit, 'CPGPFitter', batched_cp)
+      _set(ref_moo_bandit, 'CPGPFitter', batched_cp)
   return patched
 
 
@@ -455,6 +471,99 @@ def make_batched_fitter(ref_fitter_cls):
       return cts, dscr, [None] * len(cts), probs
 
   return BatchedEuclideanGPFitter
+
+
+class _CPKernelMeanNoise(object):
+  """ _KernelMeanNoise with CPGP's constructor signature (gp/cartesian_product_gp.py:211-213): what the CP fitter's
+      build_gp hands to its GP, kept and nothing else. """
+  __slots__ = ('kernel', 'mean_func', 'noise_var', 'handle_non_psd_kernels', 'host_kernel')
+
+  def __init__(self, X, Y, kernel, mean_func, noise_var, domain_lists_of_dists=None, build_posterior=True, reporter=None,
+               handle_non_psd_kernels='project_first'):
+    # pylint: disable=unused-argument
+    if build_posterior:
+      raise RuntimeError('dragonfly_amd.install: the candidate stand-in was asked for a real GP')
+    self.kernel, self.mean_func, self.noise_var = kernel, mean_func, noise_var
+    self.handle_non_psd_kernels = handle_non_psd_kernels
+    from .kernel import CartesianProductKernel
+    # (cartesian_product_gp._uses_descriptor: our mirror, every part described, no part given by distances)
+    self.host_kernel = not (isinstance(kernel, CartesianProductKernel) and kernel.has_device_spec() and
+                            all(dists is None for dists in domain_lists_of_dists or []))
+
+
+def make_batched_cp_fitter(ref_fitter_cls):
+  """ A subclass of the reference's CPGPFitter (gp/cartesian_product_gp.py:322-377) whose maximum-likelihood tuners see
+      their objective as a batch: the machinery of make_batched_fitter -- the vectorised random search for 'rand' and
+      'rand_exp_sampling', the batched tree search for 'pdoo' and the 'direct' fall-back, the speculative slice sampler
+      -- over a batch objective that takes (kernel, mean, noise) of every candidate from the reference's own build_gp
+      through a stand-in for the GP constructor and evaluates the list in ONE dfh_gp_lml_batch call with the
+      projection flag.  The points are packed once per data set (the category codes do not depend on the
+      hyper-parameters).  Candidates whose kernel has no device description take one fit each. """
+  from .engine import get_engine
+  base = make_batched_fitter(ref_fitter_cls)
+
+  class BatchedCPGPFitter(base):
+    """ dragonfly.gp.cartesian_product_gp.CPGPFitter with batched ML tuning (dragonfly_amd.install). """
+
+    def _decode_candidates(self, cts_hps_list, dscr_hps, per_cand, other_gp_params):
+      return None                    # (the short cut of the Euclidean fitter's own factory does not apply)
+
+    def _packed_points(self, kernel):
+      cached = getattr(self, '_amd_packed', None)
+      if cached is None or cached[0] is not self.X or cached[1] != len(self.X):
+        cached = self._amd_packed = (self.X, len(self.X), get_engine().to_device(kernel.pack(self.X)))
+      return cached[2]
+
+    def _lml_batch(self, cts_hps_list, dscr_hps, other_gp_params=None):
+      per_cand = len(dscr_hps) > 0 and isinstance(dscr_hps[0], (list, tuple, np.ndarray))
+      if len(cts_hps_list) == 0:
+        return np.zeros((0,))
+      user_mean = getattr(self.options, 'mean_func', None) is not None
+      import dragonfly.gp.cartesian_product_gp as _ref_cpgp
+      saved_cls = _ref_cpgp.CPGP
+      _ref_cpgp.CPGP = _CPKernelMeanNoise
+      specs, means, noises, mode, first_kernel = [], [], [], None, None
+      try:
+        for i, cts in enumerate(cts_hps_list):
+          dscr = list(dscr_hps[i]) if per_cand else list(dscr_hps)
+          gp = self.build_gp(cts, dscr, other_gp_params=other_gp_params, build_posterior=False)
+          if user_mean or getattr(gp, 'host_kernel', True) or (mode is not None and gp.handle_non_psd_kernels != mode):
+            specs = None
+            break
+          mode = gp.handle_non_psd_kernels
+          first_kernel = first_kernel or gp.kernel
+          specs.append(gp.kernel.to_spec())
+          means.append(float(gp.mean_func([self.X[0]])[0]))
+          noises.append(float(gp.noise_var))
+      finally:
+        _ref_cpgp.CPGP = saved_cls
+      if specs is None:
+        # an arbitrary mean function, or a kernel the host evaluates: one fit per candidate
+        return np.array([self._tuning_objective(c, list(dscr_hps[j]) if per_cand else list(dscr_hps),
+                                                other_gp_params=other_gp_params)
+                         for j, c in enumerate(cts_hps_list)])
+      lmls = get_engine().gp_lml_batch(specs, self._packed_points(first_kernel), self._labels_array(), means, noises,
+                                       handle_non_psd_kernels=mode)
+      if gaplog.ENABLED and len(lmls) >= 16:
+        gaplog.top2('hp_batch', lmls)
+      return lmls
+
+    def _optimise_cts_hps_for_given_dscr_hps(self, given_dscr_hps):
+      """ gp_core.py:576-583 with the batch objective. """
+      if not getattr(self, '_batched_ml', False):
+        return ref_fitter_cls._optimise_cts_hps_for_given_dscr_hps(self, given_dscr_hps)
+      objective = lambda arg: self._lml_batch(arg, list(given_dscr_hps))
+      val, cts_hps, _ = self.cts_hp_optimise(objective, self.hp_tune_max_evals)
+      return val, cts_hps, None
+
+    def _sample_cts_dscr_hps_for_rand_exp_sampling(self):
+      """ gp_core.py:585-590 with the batch objective. """
+      if not getattr(self, '_batched_ml', False):
+        return ref_fitter_cls._sample_cts_dscr_hps_for_rand_exp_sampling(self)
+      cts, dscr, probs = self.hp_sampler(self._lml_batch, self.hp_tune_max_evals)
+      return cts, dscr, [None] * len(cts), probs
+
+  return BatchedCPGPFitter
 
 
 def uninstall():

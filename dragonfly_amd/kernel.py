@@ -1,5 +1,6 @@
-"""Euclidean kernels evaluated on the MI355X: SE, Matern, Polynomial, Exponential-decay, Additive,
-coordinate-wise Product and ESP (elementary symmetric polynomial of 1-D kernels).
+"""Kernels evaluated on the MI355X: SE, Matern, Polynomial, Exponential-decay, Additive, coordinate-wise
+Product and ESP (elementary symmetric polynomial of 1-D kernels) on Euclidean inputs, the Hamming kernel on
+categorical ones, and the Cartesian-product kernel over the parts of a mixed domain.
 
 Host-side counterpart of dragonfly/gp/kernel.py: the class names, constructor arguments, the
 `hyperparams` dictionary, the printed form and the error behaviour are the reference's (its lines
@@ -287,6 +288,9 @@ def _factor_kind(kern):
   if name == 'ExpDecayKernel' and all(k in hps for k in ('scale', 'offset', 'powers')):
     if len(np.ravel(hps['powers'])) <= 8:
       return 'expdecay'
+  if isinstance(kern, HammingKernel) and 1 <= len(np.ravel(hps['dim_weights'])) <= HAMMING_DEVICE_MAX_DIM and \
+     _engine_knows_hamming():
+    return 'hamming'
   return None
 
 
@@ -299,6 +303,8 @@ def _factor_fields(kern, kind):
     return hps['scale'], hps['nu'], np.ravel(np.asarray(hps['dim_bandwidths'], dtype=float))
   if kind == 'poly':
     return hps['scale'], float(hps['order']), np.ravel(np.asarray(hps['dim_scalings'], dtype=float))
+  if kind == 'hamming':
+    return 1.0, 0.0, np.ravel(np.asarray(hps['dim_weights'], dtype=float))
   return hps['scale'], float(hps['offset']), np.ravel(np.asarray(hps['powers'], dtype=float))
 
 
@@ -571,3 +577,194 @@ class ESPKernelMatern(ESPKernel):
   def __init__(self, dim, nu, scale, order, dim_bandwidths):
     kernel_list = [MaternKernel(1, nu[i], 1.0, _esp_bandwidth(dim_bandwidths, i)) for i in range(dim)]
     super(ESPKernelMatern, self).__init__(scale, order, kernel_list)
+
+
+# ---- categorical inputs and Cartesian-product domains ---------------------------------------------------------------
+HAMMING_DEVICE_MAX_DIM = 32        # csrc/common.h: HAMMING_MAX_DIM
+
+
+def _engine_knows_hamming():
+  """ The engine in use evaluates DFH_KERNEL_HAMMING and takes the projection flags in gp_fit (engine.Engine does; an
+      engine object written against the earlier interface says nothing, and kernels with a Hamming part then stay in
+      host-kernel mode with it, as they were before the kind existed). """
+  return 'hamming' in getattr(get_engine(), 'kernel_kinds', ())
+
+
+class CategoryCoder(object):
+  """ Integer codes for the categories of each column of a discrete part, so that the device can compare them
+      as doubles.  Two items share a code exactly when the reference calls them equal: pairwise_hamming_kernel
+      (general_utils.py:113-145) compares the elements of np.array(X, dtype=object) with np.equal, i.e. with the
+      items' own `==` -- 1 == 1.0 (one code), 1 != '1' (two codes), and an np.str_ out of a string-coerced array
+      equals the same str.  The dictionary of a column grows by first appearance, so training points, test points
+      and points added later share codes.  Items that cannot be dictionary keys (unhashable, or not equal to
+      themselves such as nan) have no faithful code: ValueError, and the caller stays on the host. """
+
+  def __init__(self):
+    self.columns = []
+
+  def encode(self, part_points):
+    """ part_points: one list (or 1-D array) of items per point -> float64 [n x dim] of codes. """
+    rows = np.array([list(pt) for pt in part_points], dtype=object)
+    if rows.ndim != 2:
+      raise ValueError('The points of a discrete part must all have the same number of items.')
+    n, dim = rows.shape
+    while len(self.columns) < dim:
+      self.columns.append({})
+    out = np.empty((n, dim), dtype=np.float64)
+    for c in range(dim):
+      codes = self.columns[c]
+      for i in range(n):
+        item = rows[i, c]
+        try:
+          if not item == item:
+            raise ValueError('An item that is not equal to itself has no category code: %r.' % (item,))
+          code = codes.get(item)
+          if code is None:
+            code = codes[item] = len(codes)
+        except TypeError:
+          raise ValueError('An unhashable item has no category code: %r.' % (item,))
+        out[i, c] = code
+    return out
+
+
+class HammingKernel(Kernel):
+  """ The Hamming kernel sum_c w_c [x_c == y_c] on lists of categories (kernel.py:436-457).  A call on lists of
+      items codes them (CategoryCoder, owned by this object) and compares the codes on the device. """
+
+  def __init__(self, dim_weights):
+    super(HammingKernel, self).__init__()
+    if isinstance(dim_weights, (int, float)):
+      dim_weights = np.ones((dim_weights,))/float(dim_weights)
+    dim_weights = np.array(dim_weights)
+    self.set_hyperparams(dim_weights=dim_weights)
+    self.coder = CategoryCoder()
+
+  @property
+  def dim(self):
+    return len(self.hyperparams['dim_weights'])
+
+  def is_guaranteed_psd(self):
+    return True
+
+  def has_device_spec(self):
+    return _factor_kind(self) == 'hamming'
+
+  def to_spec(self, in_dim=None):
+    weights = np.ravel(np.asarray(self.hyperparams['dim_weights'], dtype=float))
+    return KernelSpec('hamming', weights.size, 1.0, weights, nu=0.0)
+
+  def pack(self, X):
+    """ The points' category codes as the n x dim matrix the device compares. """
+    return self.coder.encode(X)
+
+  def _child_evaluate(self, X1, X2):
+    A = self.pack(X1)
+    B = A if X2 is X1 else self.pack(X2)
+    if A.shape[1] != B.shape[1]:
+      raise ValueError('Second dimension of X1 and X2 should be equal.')
+    if not self.has_device_spec():
+      return self._host_compose(A, B)
+    return get_engine().kernel_matrix(self.to_spec(), A, None if X2 is X1 else B)
+
+  def _host_compose(self, A, B):
+    """ general_utils.py:113-145 on the codes, for host-kernel mode (more than 32 columns, or an engine object
+        that does not know the kind): the weighted matches of every row of the smaller operand, a row at a time """
+    weights = np.ravel(np.asarray(self.hyperparams['dim_weights'], dtype=float))
+    small, large, flip = (A, B, True) if len(B) < len(A) else (B, A, False)
+    ret = np.zeros((len(large), len(small)))
+    for idx, vec in enumerate(small):
+      ret[:, idx] = (np.equal(large, vec) * weights).sum(axis=1)
+    return ret.T if flip else ret
+
+  def __str__(self):
+    return 'Hamming: wts=%s'%('[' + ' '.join('%0.3f'%(w) for w in np.ravel(self.hyperparams['dim_weights'])) + ']')
+
+
+class CartesianProductKernel(Kernel):
+  """ scale * prod_j k_j(part j of x, part j of y) over the parts of a Cartesian-product domain (kernel.py:504-538).
+      Every point is a list of per-part lists.  When every part is an SE, Matern, exponential-decay or Hamming
+      mirror (an additive kernel of SE / Matern / polynomial groups too), the parts are laid side by side as
+      column groups of ONE product descriptor and the kernel is evaluated by the device in one launch per matrix;
+      with any other part the product is composed on the host from the parts' own evaluations, as the reference
+      does, and GPs using it run in host-kernel mode. """
+  _factor_kinds = ('se', 'matern', 'expdecay', 'hamming')
+
+  def __init__(self, scale, kernel_list):
+    super(CartesianProductKernel, self).__init__()
+    self.kernel_list = kernel_list
+    self.num_kernels = len(kernel_list)
+    self.add_hyperparams(scale=scale)
+
+  def is_guaranteed_psd(self):
+    return all(kern.is_guaranteed_psd() for kern in self.kernel_list)
+
+  def _part_dim(self, kern):
+    kind = _factor_kind(kern)
+    if kind == 'hamming':
+      return len(np.ravel(kern.hyperparams['dim_weights']))
+    return int(kern.dim)
+
+  def has_device_spec(self):
+    for kern in self.kernel_list:
+      if CoordinateProductKernel._additive_factor(kern):
+        if not all(_factor_kind(k) in AdditiveKernel._factor_kinds for k in kern.kernel_list):
+          return False
+      elif _factor_kind(kern) not in self._factor_kinds:
+        return False
+    return len(self.kernel_list) > 0
+
+  def part_offsets(self):
+    """ First column of every part in the packed matrix, and the total width. """
+    offs, at = [], 0
+    for kern in self.kernel_list:
+      offs.append(at)
+      at += self._part_dim(kern)
+    return offs, at
+
+  def _as_coordinate_product(self):
+    offs, total = self.part_offsets()
+    coords = [list(range(o, o + self._part_dim(k))) for o, k in zip(offs, self.kernel_list)]
+    return CoordinateProductKernel(total, self.hyperparams['scale'], self.kernel_list, coords)
+
+  def to_spec(self, in_dim=None):
+    """ One DFH_KERNEL_PRODUCT over the packed columns: part j is the column group [offset_j, offset_j + dim_j). """
+    if not self.has_device_spec():
+      raise TypeError('This Cartesian-product kernel has a part the device does not evaluate.')
+    inner = self._as_coordinate_product()
+    inner._factor_kinds = self._factor_kinds
+    return inner.to_spec(in_dim=None)
+
+  def pack(self, X):
+    """ The reference's list-of-lists points as the dense n x d matrix of to_spec: Euclidean, integral and
+        discrete-numeric parts become floats, the items of a Hamming part that kernel's category codes. """
+    offs, total = self.part_offsets()
+    out = np.empty((len(X), total), dtype=np.float64)
+    for j, (kern, off) in enumerate(zip(self.kernel_list, offs)):
+      part = [pt[j] for pt in X]
+      width = self._part_dim(kern)
+      if _factor_kind(kern) == 'hamming':
+        block = kern.pack(part)
+      else:
+        block = np.asarray(part, dtype=np.float64).reshape((len(X), -1))
+      if block.shape[1] != width:
+        raise ValueError('Part %d of the points has %d columns, its kernel %d.' % (j, block.shape[1], width))
+      out[:, off:off + width] = block
+    return out
+
+  def _host_compose(self, X1, X2):
+    """ kernel.py:525-533 with every part evaluated by its own class """
+    result = self.hyperparams['scale'] * np.ones((len(X1), len(X2)))
+    for idx, kern in enumerate(self.kernel_list):
+      result *= kern([pt[idx] for pt in X1], [pt[idx] for pt in X2])
+    return result
+
+  def _child_evaluate(self, X1, X2):
+    if not self.has_device_spec():
+      return self._host_compose(X1, X2)
+    A = self.pack(X1)
+    B = None if X2 is X1 else self.pack(X2)
+    return get_engine().kernel_matrix(self.to_spec(), A, B)
+
+  def __str__(self):
+    kernels_str = ', '.join([str(kern) for kern in self.kernel_list])
+    return 'DomProd scale=%0.2f, '%(self.hyperparams['scale']) + kernels_str

@@ -61,6 +61,16 @@ extern "C" {
                                * column per group, in column order); sub_kind[g] SE | MATERN with
                                * sub_scale / sub_nu / sub_bw that 1-D kernel's scale, nu, bandwidth;
                                * group_factor / factor_is_sum / factor_scale NULL.               */
+#define DFH_KERNEL_HAMMING  7 /* dragonfly/gp/kernel.py:436-457 HammingKernel (utils/general_utils.py:113-145):
+                               * k(x, y) = sum_c w_c [x_c == y_c] over the dim columns, which hold category
+                               * codes stored as doubles and are compared for exact equality; the terms are
+                               * added in the order of NumPy's (eq * wts).sum(axis=1).  `bw` = dim_weights,
+                               * `scale` must be 1 and `nu` 0, dim <= 32.  k(x, x) = sum_c w_c for every x.
+                               * Accepted alone and as a factor of a PRODUCT (sub_kind, with sub_bw = the
+                               * weights, sub_scale = 1, sub_nu = 0): with SE / Matern / EXPDECAY factors over
+                               * other column groups that is the reference's CartesianProductKernel
+                               * (kernel.py:504-538).  Not a group of an ADDITIVE kernel or additive factor,
+                               * not an ESP member, not in the add-UCB entry points: DFH_ERR_BAD_ARG.       */
 
 /* One Euclidean kernel.  For SE / MATERN: `dim`, `scale`, `nu`, `bw[dim]` (dim_bandwidths); POLY /
  * EXPDECAY reuse `nu` and `bw` as described above.
@@ -77,7 +87,7 @@ typedef struct dfh_kernel_desc {
   int32_t n_groups;       /* ADDITIVE only                                                   */
   const int32_t* group_off;   /* [n_groups+1]                                                */
   const int32_t* group_dims;  /* [group_off[n_groups]] column indices                        */
-  const int32_t* sub_kind;    /* [n_groups] SE | MATERN (| POLY | EXPDECAY in a PRODUCT)     */
+  const int32_t* sub_kind;    /* [n_groups] SE | MATERN (| POLY | EXPDECAY | HAMMING in a PRODUCT) */
   const double*  sub_scale;   /* [n_groups]                                                  */
   const double*  sub_nu;      /* [n_groups]                                                  */
   const double*  sub_bw;      /* [group_off[n_groups]]                                       */
@@ -177,8 +187,14 @@ int dfh_solve_triangular(dfh_ctx* ctx, const double* L, int64_t n, int upper,
 
 /* ---- GP fit / posterior ----------------------------------------------------------------- */
 #define DFH_FIT_NO_JITTER 1  /* report DFH_ERR_NOT_PD instead of running the jitter ladder    */
-/* dfh_gp_fit_gram only -- kernels that are not guaranteed PSD (Cartesian-product / neural-network
- * GPs), _get_cholesky_decomp's other branches (gp/gp_core.py:827-840):                        */
+/* Kernels that are not guaranteed PSD (Cartesian-product / neural-network GPs), _get_cholesky_decomp's
+ * other branches (gp/gp_core.py:827-840).  Honoured by dfh_gp_fit_gram, and by dfh_gp_fit and
+ * dfh_gp_lml_batch, which build the Gram matrix on the device from the descriptor first.  A handle
+ * that dfh_gp_fit made with one of them keeps its kernel and inputs: predictions, acquisitions and
+ * dfh_gp_get work on it (DFH_GET_K is the kernel matrix itself, not its projection); its hallucinated
+ * posteriors and dfh_gp_append rebuild the extended matrix from scratch under the same flag, because
+ * a projection is not a block-row update.  In dfh_gp_lml_batch every candidate of a call with one
+ * of them is fitted on its own.                                                                 */
 #define DFH_FIT_PROJECT_FIRST      2  /* 'project_first': K -> its projection onto the PSD cone
                                          (dfh_project_psd), then K + noise I and the ladder     */
 #define DFH_FIT_TRY_BEFORE_PROJECT 4  /* 'try_before_project': plain Cholesky of K + noise I; only
