@@ -18,6 +18,7 @@ KERNEL_ESP = 6
 KERNEL_HAMMING = 7
 ACQ_MEAN, ACQ_UCB, ACQ_EI, ACQ_PI, ACQ_TTEI, ACQ_STD = 0, 1, 2, 3, 4, 5
 GET_L, GET_ALPHA, GET_K = 0, 1, 2
+MO_LIN, MO_TCH, MO_MAX_OBJECTIVES = 0, 1, 8
 FIT_NO_JITTER, FIT_PROJECT_FIRST, FIT_TRY_BEFORE_PROJECT = 1, 2, 4
 LML_X_IS_DEVICE, LML_Y_IS_HOST = 0x100, 0x200       # include/dfhip.h: pointer-kind hints of dfh_gp_lml_batch
 T_NAMES = ['kernmat', 'chol', 'solve', 'cross', 'trsm', 'acq', 'ts', 'spare']
@@ -103,6 +104,11 @@ SIGNATURES = {
                           C.c_void_p, C.c_void_p, c_double_p, c_int64_p, c_int32_p]),
   'dfh_gp_add_ucb_group': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
                                      C.c_void_p, c_double_p, c_int64_p]),
+  'dfh_mo_ucb_argmax': (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_int64_p]),
+  'dfh_mo_ts_argmax': (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, c_double_p, c_int64_p, C.c_void_p]),
   # multi-GPU: host-only contract, one-process-per-GPU communicator, in-process fan-out
   'dfh_shard_bounds': (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int64, c_int64_p, c_int64_p]),
   'dfh_reduce_argmax': (C.c_int, [c_double_p, c_int64_p, C.c_int, c_double_p, c_int64_p]),

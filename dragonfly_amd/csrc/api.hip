@@ -313,7 +313,7 @@ int halluc_prepare(dfh_gp* gp, const double* Xh_user, int64_t q, Halluc* h) {
 int posterior_chunk(dfh_gp* gp, const double* Xs_dev, int64_t mc, int64_t ldxs, int part_lo, int part_hi,
                     bool pre_gathered, bool want_var, const Halluc* h, double** Kct_out,
                     double* mu_raw, double* ss, double* ss2, int parity = 0, double** Xsp_out = nullptr,
-                    double** Nsp_out = nullptr) {
+                    double** Nsp_out = nullptr, double** T_out = nullptr) {
   dfh_ctx* ctx = gp->ctx;
   const KernDev& kd = gp->kd;
   double* Xsp = nullptr; double* Nsp = nullptr; double* Kct = nullptr;
@@ -343,12 +343,13 @@ int posterior_chunk(dfh_gp* gp, const double* Xs_dev, int64_t mc, int64_t ldxs, 
     if (h && h->q > 0) {
       const int64_t q = h->q;
       double* T = nullptr;
-      DFH_TRY(scratch_get(ctx, SCR_AUG2, (size_t)mc * q * 8, (void**)&T));
+      DFH_TRY(scratch_get(ctx, parity ? SCR_AUG2B : SCR_AUG2, (size_t)mc * q * 8, (void**)&T));
       // T = k(Xs, Xh) - V1t Wt^T
       DFH_TRY(kernmat_packed(ctx, kd, 0, kd.n_parts, true, Xsp, Nsp, mc, h->Xhp, h->Nhp, q, false, 0.0, T, q));
       DFH_TRY(gemm_f64(ctx, 0, mc, q, gp->n, -1.0, Kct, gp->n, h->Wt, gp->n, 1.0, T, q, T, q));
       hipLaunchKernelGGL(k_halluc_rows, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, T, (long)mc, (int)q, h->Lh, ss2);
       DFH_LAUNCH_CHECK();
+      if (T_out) *T_out = T;        // V2^T: the rows solved against Lh
     }
   }
   if (Kct_out) *Kct_out = Kct;
@@ -367,6 +368,84 @@ int ladder_pow(int p, double max_M, double* out) {
   *out = pow(10.0, (double)p) * max_M;      // (10 ** diag_noise_power) * max_M, general_utils.py:189
   return DFH_OK;
 }
+
+// Multi-objective scalarisations (opt/multiobjective_gpb_acquisitions.py:19-107), one value per candidate from the k
+// rows of A (posterior means, or joint draws) and S (posterior standard deviations; UCB only), row i at i * ld.
+// The reference's order of operations, quirks included: the Tchebychev UCB takes the square root of the standard
+// deviation (:102-103); np.minimum gives NaN when either operand is NaN.
+struct MoParams { double w[DFH_MO_MAX_OBJECTIVES]; double ref[DFH_MO_MAX_OBJECTIVES]; };
+__device__ __forceinline__ double np_minimum(double a, double b) {
+  if (a != a) return a;
+  if (b != b) return b;
+  return a < b ? a : b;
+}
+__global__ void k_mo_scalarise(int scal, int ucb, int k, double beta, MoParams par, const double* __restrict__ A,
+                               const double* __restrict__ S, long ld, long m, double* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  double v;
+  if (scal == DFH_MO_LIN) {
+    double tot = 0.0, s2 = 0.0;
+    for (int j = 0; j < k; ++j) {
+      const double w = par.w[j];
+      tot = tot + A[j * ld + i] * w;                         // :38 (s += sample * weight), :86 (mu_tot += mu * weight)
+      if (ucb) { const double sd = S[j * ld + i]; s2 = s2 + (sd * sd) * (w * w); }   // :87
+    }
+    v = ucb ? tot + beta * sqrt(s2) : tot;                   // :88
+  } else {
+    v = INFINITY;                                            // :61, :99
+    for (int j = 0; j < k; ++j) {
+      double t = A[j * ld + i];
+      if (ucb) t = t + beta * sqrt(S[j * ld + i]);           // :103, the square root of 'std' as there
+      v = np_minimum(v, (t - par.ref[j]) / par.w[j]);        // :64, :103-104
+    }
+  }
+  out[i] = v;
+}
+
+// What both multi-objective entry points demand of their arguments (include/dfhip.h)
+int mo_check(dfh_gp* const* gps, int32_t k, int scal, const double* weights, const double* refs, MoParams* par) {
+  DFH_ARG(gps && k >= 1 && k <= DFH_MO_MAX_OBJECTIVES && weights);
+  DFH_ARG(scal == DFH_MO_LIN || scal == DFH_MO_TCH);
+  DFH_ARG(scal == DFH_MO_LIN || refs);
+  for (int i = 0; i < k; ++i) {
+    DFH_ARG(gps[i] && !gps[i]->gram);            // needs the kernels
+    DFH_ARG(gps[i]->ctx == gps[0]->ctx && gps[i]->d == gps[0]->d);
+    DFH_ARG(scal == DFH_MO_LIN || weights[i] != 0.0);
+    par->w[i] = weights[i];
+    par->ref[i] = (scal == DFH_MO_TCH) ? refs[i] : 0.0;
+  }
+  for (int i = k; i < DFH_MO_MAX_OBJECTIVES; ++i) { par->w[i] = 0.0; par->ref[i] = 0.0; }
+  return DFH_OK;
+}
+
+// Rows per posterior chunk with K fitted GPs resident: pick_chunk's figure, and never more than an eighth of what
+// is free NOW -- with the K factors (K x n^2 x 8 bytes), their block inverses and everything else the caller keeps in
+// HBM already taken out -- plus the context's own scratch, which the chunk reuses.
+int64_t mo_pick_chunk(dfh_ctx* ctx, int64_t n_max, int64_t m) {
+  int64_t mc = pick_chunk(ctx, n_max, m);
+  size_t f = 0, t = 0;
+  if (hipMemGetInfo(&f, &t) == hipSuccess) {
+    size_t own = 0;
+    for (const DevBuf& b : ctx->scratch) own += b.bytes;
+    int64_t cap = (int64_t)((f + own) / 8 / ((size_t)(n_max > 0 ? n_max : 1) * 8));
+    cap = std::max<int64_t>(512, (cap / 512) * 512);
+    if (mc > cap) mc = cap;
+  } else {
+    (void)hipGetLastError();
+  }
+  return mc;
+}
+
+struct DevBlock {           // dev_alloc'ed memory of one call
+  dfh_ctx* ctx; void* p = nullptr;
+  explicit DevBlock(dfh_ctx* c) : ctx(c) {}
+  ~DevBlock() {             // (a block goes back to the cache only once nothing in flight can touch it)
+    if (!p) return;
+    (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->bulk);
+    dev_release(ctx, p);
+  }
+};
 
 }  // namespace
 
@@ -1875,15 +1954,19 @@ extern "C" int dfh_gp_predict_covar(dfh_gp* gp, const double* Xs, int64_t m, con
   return DFH_OK;
 }
 
-extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block, const double* U,
-                         double mean_const, const double* mean_vals, double* samples_out, double* best_val,
-                         int64_t* best_idx, int32_t* jitter_powers_out) {
-  DFH_ARG(gp && Xs && U && m >= 1 && block >= 1);
-  DFH_ARG(!gp->gram);      // needs the kernel: this posterior was built from a Gram matrix
+// The blocked-joint draw of dfh_gp_ts (include/dfhip.h) for one GP.  `gp` gives the mean; the block covariances come from
+// `cov_gp`'s factor -- gp itself, or the augmented GP of the hallucination's fall-back (halluc_augmented_gp) -- and, with
+// `h` (halluc_prepare's block form of the q in-progress points, gp_core.py:192-220), lose the rank-q term V2^T V2 as well.
+// samples_dev (optional, device [m]) receives the draw without a trip to the host; the arg-max is skipped when neither
+// best_val nor best_idx is wanted (the multi-objective call scalarises K draws first).
+static int ts_run(dfh_gp* gp, dfh_gp* cov_gp, const Halluc* h, const double* Xs, int64_t m, int64_t block, const double* U,
+                  double mean_const, const double* mean_vals, double* samples_dev, double* samples_out, double* best_val,
+                  int64_t* best_idx, int32_t* jitter_powers_out) {
   dfh_ctx* ctx = gp->ctx;
   DFH_HIP(hipSetDevice(ctx->device));
-  const KernDev& kd = gp->kd;
-  const int64_t n = gp->n;
+  const KernDev& kd = cov_gp->kd;
+  const int64_t n = cov_gp->n;
+  const int64_t hq = (h && cov_gp == gp) ? h->q : 0;
   if (block > m) block = m;
   DFH_ARG((double)block * (double)block * 8.0 < 32e9);
   // several TS blocks share one posterior chunk so the TRSM runs on big GEMMs
@@ -1893,8 +1976,8 @@ extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
   const bool xs_dev = is_device_ptr(Xs), u_dev = is_device_ptr(U);
   const bool mv_dev = mean_vals ? is_device_ptr(mean_vals) : true;
   double* vec[2] = {nullptr, nullptr};
-  DFH_TRY(scratch_get(ctx, SCR_VEC, (size_t)mc_max * 8 * 2, (void**)&vec[0]));
-  DFH_TRY(scratch_get(ctx, SCR_VECB, (size_t)mc_max * 8 * 2, (void**)&vec[1]));
+  DFH_TRY(scratch_get(ctx, SCR_VEC, (size_t)mc_max * 8 * 3, (void**)&vec[0]));      // mu | draw | spare (ss2 / unused mean)
+  DFH_TRY(scratch_get(ctx, SCR_VECB, (size_t)mc_max * 8 * 3, (void**)&vec[1]));
   // up to DFH_TS_BATCH (64) blocks of a chunk are factored as one lock-step batch
   static const int ts_batch = []() { const char* e = getenv("DFH_TS_BATCH"); int v = e ? atoi(e) : 64; return v < 1 ? 1 : (v > CHOL_MAX_BATCH ? CHOL_MAX_BATCH : v); }();
   const int64_t lb_slots = std::max<int64_t>(1, std::min<int64_t>(ts_batch, mc_max / block));
@@ -1906,7 +1989,7 @@ extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
   // look-ahead factorisation, host-synchronous because of the jitter ladder) and the draw.
   // The factorisations hide behind the next chunk's TRSM instead of idling the GPU.
   hipStream_t mainS = ctx->stream, bulkS = ctx->bulk;
-  struct Stage1 { double* Kct; double* Xsp; double* Nsp; double* mu; };
+  struct Stage1 { double* Kct; double* Xsp; double* Nsp; double* mu; double* T; };
   Stage1 st[2];
   hipEvent_t ev_in, ev_ready[2], ev_free[2];
   DFH_TRY(ctx_event(ctx, EV_TS_BASE, &ev_in));
@@ -1927,8 +2010,16 @@ extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
     if (xs_dev) xs_c = Xs + i0 * gp->d;
     else DFH_TRY(to_device(ctx, Xs + i0 * gp->d, (size_t)mc * gp->d * 8, p ? SCR_STAGE_A2 : SCR_STAGE_A, &xs_c));
     st[p].mu = vec[p];
-    DFH_TRY(posterior_chunk(gp, xs_c, mc, gp->d, 0, kd.n_parts, false, true, nullptr, &st[p].Kct, st[p].mu,
-                            nullptr, nullptr, p, &st[p].Xsp, &st[p].Nsp));
+    st[p].T = nullptr;
+    if (cov_gp != gp) {
+      // mean from the real data, V^T from the augmented factor (gp_core.py:195, 207-213); same parity buffers, in this order
+      DFH_TRY(posterior_chunk(gp, xs_c, mc, gp->d, 0, kd.n_parts, false, false, nullptr, nullptr, st[p].mu, nullptr, nullptr, p));
+      DFH_TRY(posterior_chunk(cov_gp, xs_c, mc, gp->d, 0, kd.n_parts, false, true, nullptr, &st[p].Kct, vec[p] + 2 * mc_max,
+                              nullptr, nullptr, p, &st[p].Xsp, &st[p].Nsp));
+    } else {
+      DFH_TRY(posterior_chunk(gp, xs_c, mc, gp->d, 0, kd.n_parts, false, true, hq > 0 ? h : nullptr, &st[p].Kct, st[p].mu,
+                              nullptr, vec[p] + 2 * mc_max, p, &st[p].Xsp, &st[p].Nsp, &st[p].T));
+    }
     DFH_HIP(hipEventRecord(ev_ready[p], bulkS));
     return DFH_OK;
   };
@@ -1968,7 +2059,10 @@ extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
       const double* Vt = Kct + b0 * n;
       auto build_sigma = [&]() -> int {
         DFH_TRY(sigma_kernel(b0, B, dst));
-        return gemm_f64(ctx, GEMM_LOWER, B, B, n, -1.0, Vt, n, Vt, n, 1.0, dst, B, dst, B);
+        DFH_TRY(gemm_f64(ctx, GEMM_LOWER, B, B, n, -1.0, Vt, n, Vt, n, 1.0, dst, B, dst, B));
+        if (hq == 0) return DFH_OK;
+        const double* V2t = st[p].T + b0 * hq;           // second block row of the augmented solve: Sigma -= V2^T V2
+        return gemm_f64(ctx, GEMM_LOWER, B, B, hq, -1.0, V2t, hq, V2t, hq, 1.0, dst, B, dst, B);
       };
       DFH_TRY(build_sigma());
       int32_t jp = INT32_MIN;
@@ -1994,7 +2088,12 @@ extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
           GemmBatch bs;
           bs.count = nb; bs.sA = bs.sB = B * n; bs.sCin = bs.sCout = B * B;
           const double* Vt = Kct + g0 * B * n;
-          return gemm_f64(ctx, GEMM_LOWER, B, B, n, -1.0, Vt, n, Vt, n, 1.0, Lb, B, Lb, B, &bs);
+          DFH_TRY(gemm_f64(ctx, GEMM_LOWER, B, B, n, -1.0, Vt, n, Vt, n, 1.0, Lb, B, Lb, B, &bs));
+          if (hq == 0) return DFH_OK;
+          GemmBatch bh;
+          bh.count = nb; bh.sA = bh.sB = B * hq; bh.sCin = bh.sCout = B * B;
+          const double* V2t = st[p].T + g0 * B * hq;
+          return gemm_f64(ctx, GEMM_LOWER, B, B, hq, -1.0, V2t, hq, V2t, hq, 1.0, Lb, B, Lb, B, &bh);
         };
         DFH_TRY(build_group());
         int64_t piv[CHOL_MAX_BATCH] = {0};
@@ -2018,12 +2117,142 @@ extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
       DFH_TRY(gemv_rows(ctx, Lb, B, B, B, u_c + b0, 1.0, mu_raw + b0, 1.0, samp + b0, true));
     }
     blk_idx += (mc + block - 1) / block;
-    DFH_TRY(argmax_update(ctx, samp, mc, i0, &have, &bv, &bi));
+    if (best_val || best_idx) DFH_TRY(argmax_update(ctx, samp, mc, i0, &have, &bv, &bi));
+    if (samples_dev) DFH_HIP(hipMemcpyAsync(samples_dev + i0, samp, (size_t)mc * 8, hipMemcpyDeviceToDevice, mainS));
     if (samples_out) DFH_TRY(from_device(ctx, samples_out + i0, samp, (size_t)mc * 8));
     DFH_HIP(hipEventRecord(ev_free[p], mainS));
   }
   DFH_HIP(hipStreamSynchronize(mainS));
   DFH_HIP(hipStreamSynchronize(bulkS));
+  if (best_val) *best_val = bv;
+  if (best_idx) *best_idx = bi;
+  return DFH_OK;
+}
+
+extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block, const double* U,
+                         double mean_const, const double* mean_vals, double* samples_out, double* best_val,
+                         int64_t* best_idx, int32_t* jitter_powers_out) {
+  DFH_ARG(gp && Xs && U && m >= 1 && block >= 1);
+  DFH_ARG(!gp->gram);      // needs the kernel: this posterior was built from a Gram matrix
+  // (the arg-max always ran here, whatever the caller asked for: keep its synchronisation points)
+  double bv = 0.0; int64_t bi = -1;
+  DFH_TRY(ts_run(gp, gp, nullptr, Xs, m, block, U, mean_const, mean_vals, nullptr, samples_out, &bv, &bi, jitter_powers_out));
+  if (best_val) *best_val = bv;
+  if (best_idx) *best_idx = bi;
+  return DFH_OK;
+}
+
+// ---- multi-objective acquisitions: K fitted GPs, one call -------------------------------------------------------
+extern "C" int dfh_mo_ucb_argmax(dfh_gp* const* gps, int32_t k, int scal, double beta, const double* weights,
+                                 const double* refs, const double* Xs, int64_t m, const double* mean_consts,
+                                 const double* mean_vals, double* vals_out, double* best_val, int64_t* best_idx) {
+  MoParams par;
+  DFH_TRY(mo_check(gps, k, scal, weights, refs, &par));
+  DFH_ARG(Xs && m >= 1 && (mean_consts || mean_vals));
+  dfh_ctx* ctx = gps[0]->ctx;
+  DFH_HIP(hipSetDevice(ctx->device));
+  const int64_t d = gps[0]->d;
+  int64_t n_max = 0;
+  for (int i = 0; i < k; ++i) n_max = std::max(n_max, gps[i]->n);
+  const int64_t mc_max = mo_pick_chunk(ctx, n_max, m);
+  // the candidates (and per-candidate prior means) go to HBM once, not once per objective
+  DevBlock stage(ctx);
+  const bool xs_dev = is_device_ptr(Xs), mv_dev = mean_vals ? is_device_ptr(mean_vals) : true;
+  const size_t b_xs = xs_dev ? 0 : (size_t)m * d * 8, b_mv = mv_dev ? 0 : (size_t)k * m * 8;
+  if (b_xs + b_mv) {
+    DFH_TRY(dev_alloc(ctx, b_xs + b_mv, &stage.p));
+    char* sp = static_cast<char*>(stage.p);
+    if (b_xs) { DFH_HIP(hipMemcpyAsync(sp, Xs, b_xs, hipMemcpyHostToDevice, ctx->stream)); Xs = reinterpret_cast<const double*>(sp); }
+    if (b_mv) { DFH_HIP(hipMemcpyAsync(sp + b_xs, mean_vals, b_mv, hipMemcpyHostToDevice, ctx->stream)); mean_vals = reinterpret_cast<const double*>(sp + b_xs); }
+    DFH_HIP(hipStreamSynchronize(ctx->stream));      // pageable sources: staged before the caller's buffers may change
+  }
+  double* vec = nullptr;
+  DFH_TRY(scratch_get(ctx, SCR_VEC, (size_t)mc_max * 8 * (4 + 2 * (size_t)k), (void**)&vec));
+  double* mu_raw = vec; double* ss = vec + mc_max; double* kss_w = vec + 2 * mc_max; double* val_c = vec + 3 * mc_max;
+  double* MU = vec + 4 * mc_max; double* SD = MU + (int64_t)k * mc_max;       // [k][mc_max] each
+  bool have = false; double bv = 0.0; int64_t bi = -1;
+  for (int64_t i0 = 0; i0 < m; i0 += mc_max) {
+    const int64_t mc = std::min(mc_max, m - i0);
+    const unsigned grid = (unsigned)((mc + 255) / 256);
+    for (int i = 0; i < k; ++i) {
+      dfh_gp* gp = gps[i];
+      double* xsp = nullptr; double* nsp = nullptr;
+      // gp.eval(x, 'std'), :85 / :102 -- each objective packs the shared candidates with its own bandwidths
+      DFH_TRY(posterior_chunk(gp, Xs + i0 * d, mc, d, 0, gp->kd.n_parts, false, true, nullptr, nullptr, mu_raw, ss, nullptr,
+                              0, &xsp, &nsp));
+      double* kss = gp->kd.stationary ? nullptr : kss_w;
+      if (kss) DFH_TRY(prior_diag(ctx, gp->kd, xsp, nsp, mc, kss));
+      SectionTimer t(ctx, DFH_T_ACQ);
+      hipLaunchKernelGGL(k_posterior_acq, dim3(grid), dim3(256), 0, ctx->stream, (int)DFH_ACQ_MEAN, 0.0, 0.0, gp->kd.kxx,
+                         (const double*)kss, mean_consts ? mean_consts[i] : 0.0,
+                         mean_vals ? mean_vals + (int64_t)i * m + i0 : (const double*)nullptr, (const double*)mu_raw,
+                         (const double*)ss, (const double*)nullptr, (long)mc, MU + (int64_t)i * mc_max,
+                         SD + (int64_t)i * mc_max, (double*)nullptr);
+      DFH_LAUNCH_CHECK();
+    }
+    SectionTimer t(ctx, DFH_T_ACQ);
+    hipLaunchKernelGGL(k_mo_scalarise, dim3(grid), dim3(256), 0, ctx->stream, scal, 1, (int)k, beta, par, (const double*)MU,
+                       (const double*)SD, (long)mc_max, (long)mc, val_c);
+    DFH_LAUNCH_CHECK();
+    if (best_val || best_idx) DFH_TRY(argmax_update(ctx, val_c, mc, i0, &have, &bv, &bi));
+    if (vals_out) DFH_TRY(from_device(ctx, vals_out + i0, val_c, (size_t)mc * 8));
+  }
+  DFH_HIP(hipStreamSynchronize(ctx->stream));
+  if (best_val) *best_val = bv;
+  if (best_idx) *best_idx = bi;
+  return DFH_OK;
+}
+
+extern "C" int dfh_mo_ts_argmax(dfh_gp* const* gps, int32_t k, int scal, const double* weights, const double* refs,
+                                const double* Xs, int64_t m, int64_t block, const double* Xh, int64_t q, const double* U,
+                                const double* mean_consts, const double* mean_vals, double* vals_out, double* best_val,
+                                int64_t* best_idx, int32_t* jitter_powers_out) {
+  MoParams par;
+  DFH_TRY(mo_check(gps, k, scal, weights, refs, &par));
+  DFH_ARG(Xs && U && m >= 1 && block >= 1 && q >= 0 && (q == 0 || Xh) && (mean_consts || mean_vals));
+  dfh_ctx* ctx = gps[0]->ctx;
+  DFH_HIP(hipSetDevice(ctx->device));
+  const int64_t d = gps[0]->d;
+  if (block > m) block = m;
+  const int64_t nblk = (m + block - 1) / block;
+  // candidates (if they come from the host) | the K draws, objective-major | the scalarised values.  Memory of this
+  // call's own, not scratch: the hallucination's fall-back re-fits a GP between two objectives.
+  DevBlock hold(ctx);
+  const bool xs_dev = is_device_ptr(Xs);
+  const size_t b_xs = xs_dev ? 0 : (size_t)m * d * 8;
+  DFH_TRY(dev_alloc(ctx, b_xs + (size_t)(k + 1) * m * 8, &hold.p));
+  char* hp = static_cast<char*>(hold.p);
+  if (b_xs) { DFH_HIP(hipMemcpyAsync(hp, Xs, b_xs, hipMemcpyHostToDevice, ctx->stream)); Xs = reinterpret_cast<const double*>(hp); DFH_HIP(hipStreamSynchronize(ctx->stream)); }
+  double* S = reinterpret_cast<double*>(hp + b_xs);
+  double* vals = S + (int64_t)k * m;
+  for (int i = 0; i < k; ++i) {
+    dfh_gp* gp = gps[i];
+    // get_gp_sampler_for_parallel_strategy (:29, :54): the draw of the GP augmented with the points in progress
+    // (gp_core.py:256-261) -- block form, or the augmented GP factored from scratch where that is not positive definite
+    Halluc h;
+    dfh_gp* aug = nullptr;
+    if (q > 0) {
+      int rc = halluc_prepare(gp, Xh, q, &h);
+      if (rc == DFH_ERR_NOT_PD) {
+        h.q = 0;
+        rc = halluc_augmented_gp(gp, Xh, q, &aug);
+      }
+      DFH_TRY(rc);
+    }
+    const int rc = ts_run(gp, aug ? aug : gp, &h, Xs, m, block, U + (int64_t)i * m, mean_consts ? mean_consts[i] : 0.0,
+                          mean_vals ? mean_vals + (int64_t)i * m : nullptr, S + (int64_t)i * m, nullptr, nullptr, nullptr,
+                          jitter_powers_out ? jitter_powers_out + (int64_t)i * nblk : nullptr);
+    if (aug) dfh_gp_free(aug);
+    DFH_TRY(rc);
+  }
+  SectionTimer t(ctx, DFH_T_ACQ);
+  hipLaunchKernelGGL(k_mo_scalarise, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, scal, 0, (int)k, 0.0, par,
+                     (const double*)S, (const double*)nullptr, (long)m, (long)m, vals);
+  DFH_LAUNCH_CHECK();
+  bool have = false; double bv = 0.0; int64_t bi = -1;
+  if (best_val || best_idx) DFH_TRY(argmax_update(ctx, vals, m, 0, &have, &bv, &bi));
+  if (vals_out) DFH_TRY(from_device(ctx, vals_out, vals, (size_t)m * 8));
+  DFH_HIP(hipStreamSynchronize(ctx->stream));
   if (best_val) *best_val = bv;
   if (best_idx) *best_idx = bi;
   return DFH_OK;

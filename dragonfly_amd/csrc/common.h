@@ -142,6 +142,7 @@ enum ScratchSlot {
   SCR_RED2,         // two-stage log-determinant: per-workgroup partial sums
   SCR_YCACHE,       // labels of the last tuning call (kept across calls: a fitter asks thousands of times with the same y)
   SCR_LMLCTL,       // tuning group: results | failed pivots | status | team flags, one block (one memset, one copy back)
+  SCR_AUG2B,        // second parity of SCR_AUG2 (hallucinated Thompson sampling: the pipelined chunks)
   SCR_COUNT
 };
 

@@ -14,6 +14,7 @@ from ._lib import (ACQ_EI, ACQ_MEAN, ACQ_PI, ACQ_STD, ACQ_TTEI, ACQ_UCB, GET_ALP
                    KernelDesc,
                    check)
 
+MO_SCALARISATIONS = {'lin': _lib.MO_LIN, 'tch': _lib.MO_TCH}
 ACQ_IDS = {'mean': ACQ_MEAN, 'ucb': ACQ_UCB, 'ei': ACQ_EI, 'pi': ACQ_PI, 'ttei': ACQ_TTEI,
            'std': ACQ_STD}
 
@@ -498,6 +499,65 @@ class Engine(object):
     check(self.lib.dfh_solve_triangular(self.ctx, _ptr(L_lower), n, 1 if upper else 0, _ptr(b),
                                         nrhs, _ptr(x)))
     return x
+
+  # -- multi-objective acquisitions --------------------------------------------------------
+  @staticmethod
+  def _mo_args(gps, scal, weights, refs, Xs, mean_consts, mean_vals):
+    """ What dfh_mo_ucb_argmax and dfh_mo_ts_argmax share: the handle array, the scalarisation and its
+        parameters, the candidates and the prior means (constants, or [k x m] values). """
+    k = len(gps)
+    handles = (C.c_void_p * max(k, 1))(*[gp.handle for gp in gps])
+    if scal not in MO_SCALARISATIONS:
+      raise ValueError('Unknown scalarisation %s (lin | tch).' % (scal))
+    w = _f64(np.ravel(weights))
+    r = None if refs is None else _f64(np.ravel(refs))
+    if len(w) != k or (r is not None and len(r) != k):
+      raise ValueError('Need one weight (and one reference value) per objective.')
+    Xs = Xs if isinstance(Xs, DeviceArray) else _f64(Xs)
+    m = Xs.shape[0]
+    mv = None
+    if mean_vals is not None:
+      mv = mean_vals if isinstance(mean_vals, DeviceArray) else _f64(mean_vals)
+      if tuple(mv.shape) != (k, m):
+        raise ValueError('mean_vals must have shape (objectives, candidates).')
+    mc = _f64(np.zeros(k) if mean_consts is None else np.ravel(mean_consts))
+    if len(mc) != k:
+      raise ValueError('Need one mean constant per objective.')
+    return handles, k, MO_SCALARISATIONS[scal], w, r, Xs, m, mc, mv
+
+  def mo_ucb_argmax(self, gps, scal, beta, weights, refs, Xs, mean_consts=None, mean_vals=None, return_vals=False):
+    """ The multi-objective UCB of K FittedGPs (opt/multiobjective_gpb_acquisitions.py:76-106) over the
+        candidates Xs (host array or DeviceArray) and its arg-max in one device call.  scal 'lin' | 'tch';
+        refs may be None for 'lin'.  Returns (best_val, best_idx[, vals]). """
+    handles, k, scal_id, w, r, Xs, m, mc, mv = self._mo_args(gps, scal, weights, refs, Xs, mean_consts, mean_vals)
+    vals = np.empty(m) if return_vals else None
+    bv, bi = C.c_double(0), C.c_int64(-1)
+    check(self.lib.dfh_mo_ucb_argmax(handles, k, scal_id, float(beta), _ptr(w), _ptr(r), _ptr(Xs), m, _ptr(mc), _ptr(mv),
+                                     _ptr(vals), C.byref(bv), C.byref(bi)))
+    return (bv.value, bi.value, vals) if return_vals else (bv.value, bi.value)
+
+  def mo_thompson(self, gps, scal, weights, refs, Xs, U, block=4096, X_halluc=None, mean_consts=None, mean_vals=None,
+                  return_vals=False):
+    """ Multi-objective Thompson sampling (:19-67): objective i's blocked-joint draw from row i of the
+        standard normals U [k x m] (host array or DeviceArray), with the points in progress X_halluc
+        hallucinated into every objective's GP, scalarised, and the arg-max.  Returns (best_val, best_idx[,
+        vals, jitter_powers [k][blocks]]). """
+    handles, k, scal_id, w, r, Xs, m, mc, mv = self._mo_args(gps, scal, weights, refs, Xs, mean_consts, mean_vals)
+    Uh = U if isinstance(U, DeviceArray) else _f64(np.ravel(U))
+    if Uh.size != k * m:
+      raise ValueError('U must hold one standard normal per objective and candidate.')
+    block = int(min(block, m))
+    nblk = (m + block - 1) // block
+    Xh, q = (None, 0) if X_halluc is None or len(X_halluc) == 0 else FittedGP._rows(X_halluc)
+    vals = np.empty(m) if return_vals else None
+    jps = (C.c_int32 * (k * nblk))()
+    bv, bi = C.c_double(0), C.c_int64(-1)
+    check(self.lib.dfh_mo_ts_argmax(handles, k, scal_id, _ptr(w), _ptr(r), _ptr(Xs), m, block, _ptr(Xh), q, _ptr(Uh),
+                                    _ptr(mc), _ptr(mv), _ptr(vals), C.byref(bv), C.byref(bi), jps))
+    if return_vals:
+      powers = [[None if jps[i * nblk + b] == INT32_MIN else jps[i * nblk + b] for b in range(nblk)] for i in range(k)]
+      return bv.value, bi.value, vals, powers
+    return bv.value, bi.value
 
   # -- GP ----------------------------------------------------------------------------------
   def gp_lml_batch(self, specs, X, y, mean_consts, noise_vars, allow_jitter=True, return_powers=False,

@@ -55,6 +55,12 @@ edited):
   S4' MOO      dragonfly.opt.multiobjective_gpb_acquisitions.maximise_acquisition -> ours for
                Euclidean domains: the multi-objective closures are maximised by the batched tree
                search / the vectorised random search too.
+  S4'' MOO acquisitions  (only with install(multi_objective=True)) the four callables of the namespaces
+               dragonfly.opt.multiobjective_gpb_acquisitions.asy / seq (lin_ts, tch_ts, lin_ucb, tch_ucb) ->
+               dispatchers as in S4: dragonfly_amd.multiobjective_gpb_acquisitions on Euclidean domains -- the
+               K objectives' posteriors (or joint draws, points in progress hallucinated on the device), the
+               scalarisation and the arg-max in one device call -- the reference's own callables elsewhere.
+               Opt-in: without the flag the per-objective call stream of S4' stays exactly as it was.
 A compiled Fortran DIRECT, when present, keeps working: it calls gp.eval per point, which now
 runs on the device, through `external_maximise_with_method`.
 """
@@ -68,7 +74,7 @@ from . import gaplog
 _saved = []     # (object, attribute name, original value)
 
 
-def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False):
+def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, multi_objective=False):
   """ Rebinds the names listed above; returns the list of patched attributes. """
   import dragonfly.gp.kernel as ref_kernel
   import dragonfly.gp.euclidean_gp as ref_egp
@@ -113,6 +119,16 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False):
       return gpb_acquisitions.maximise_acquisition(acq_fn, anc_data, *args, **kwargs)
     return ref_maximise(acq_fn, anc_data, *args, **kwargs)
   _set(ref_moo_acq, 'maximise_acquisition', _moo_maximise_acquisition)
+  if multi_objective:
+    # the four acquisitions themselves, looked up with getattr in the namespaces asy / seq
+    # (opt/multiobjective_gp_bandit.py): K posteriors or draws, scalarisation and arg-max in one device call
+    from . import multiobjective_gpb_acquisitions as our_moo_acq
+    for ns_name in ('asy', 'seq'):
+      ref_ns, our_ns = getattr(ref_moo_acq, ns_name), getattr(our_moo_acq, ns_name)
+      for acq in ('lin_ts', 'tch_ts', 'lin_ucb', 'tch_ucb'):
+        _saved.append((ref_ns, acq, getattr(ref_ns, acq)))
+        setattr(ref_ns, acq, _euclidean_dispatch(getattr(our_ns, acq), getattr(ref_ns, acq)))
+        patched.append('dragonfly.opt.multiobjective_gpb_acquisitions.%s.%s' % (ns_name, acq))
   if batched_tuning:
     import dragonfly.opt.gp_bandit as ref_gp_bandit
     import dragonfly.opt.multiobjective_gp_bandit as ref_moo_bandit

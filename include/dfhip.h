@@ -329,6 +329,50 @@ int dfh_gp_add_ucb_group(dfh_gp* gp, int32_t group, double beta, const double* X
 int dfh_gp_add_ucb_all(dfh_gp* gp, const double* betas, const double* Xg_all, const int64_t* m_per_group,
                        double* vals_out, double* best_vals, int64_t* best_idx);
 
+/* ---- multi-objective acquisitions (opt/multiobjective_gpb_acquisitions.py:19-107) -----------------
+ * K fitted GPs -- one per objective: the same candidates, independent kernels and factors -- in ONE call:
+ * candidates -> K posteriors (or K joint draws) -> scalarisation -> arg-max (np.argmax's: first NaN, else
+ * first maximum).  The reference's closures call gp.eval / gp.draw_samples once per objective and scalarise
+ * K vectors of m values in NumPy.  All K handles must belong to one context and have the same input
+ * dimension, 1 <= k <= DFH_MO_MAX_OBJECTIVES; otherwise, and for a zero weight or refs == NULL under
+ * DFH_MO_TCH: DFH_ERR_BAD_ARG.  weights [k] / refs [k] (anc_data.obj_weights / .reference_point) are
+ * host arrays; mean_consts [k] are the objectives' constant prior means, mean_vals ([k x m], objective-
+ * major, host or device) replaces them when given (one of the two must be); vals_out: optional [m].
+ * The formulas are the reference's in its order of operations, sums over i = 0 .. k-1:
+ *   LIN UCB (:76-90)   (0.0 + sum mu_i w_i) + beta sqrt(0.0 + sum (sd_i sd_i)(w_i w_i))
+ *   TCH UCB (:93-106)  min_i ((mu_i + beta sqrt(sd_i) - ref_i) / w_i) from +inf -- the reference takes
+ *                      np.sqrt of what gp.eval(.., 'std') returns, the standard deviation; kept
+ *   LIN TS  (:19-41)   0.0 + sum s_i w_i
+ *   TCH TS  (:44-67)   min_i ((s_i - ref_i) / w_i) from +inf
+ * min is np.minimum: NaN when either operand is NaN.                                                  */
+#define DFH_MO_LIN 0      /* linear scalarisation      */
+#define DFH_MO_TCH 1      /* Tchebychev scalarisation  */
+#define DFH_MO_MAX_OBJECTIVES 8
+
+/* mo_lin_asy_ucb / mo_tch_asy_ucb (:76-106) + random_maximise's arg-max (utils/oper_utils.py:73).  beta is
+ * the caller's sqrt(0.2 dim log(2 dim t + 1)) (:71-73).  The closures call gp.eval, not the hallucinating
+ * wrapper: no Xh here.                                                                                */
+int dfh_mo_ucb_argmax(dfh_gp* const* gps, int32_t k, int scal, double beta,
+                      const double* weights /*[k]*/, const double* refs /*[k], TCH only*/,
+                      const double* Xs, int64_t m,
+                      const double* mean_consts /*[k]*/, const double* mean_vals /*[k x m] or NULL*/,
+                      double* vals_out /*[m] or NULL*/, double* best_val, int64_t* best_idx);
+
+/* mo_lin_asy_ts / mo_tch_asy_ts (:19-67): s_i is objective i's blocked-joint draw exactly as dfh_gp_ts
+ * defines it, from row i of U [k x m] (the reference draws objective 0's m normals, then objective 1's,
+ * ...).  With Xh (q in-progress points; get_gp_sampler_for_parallel_strategy, opt/gpb_acquisitions.py:67-87)
+ * the block covariance is that of the GP augmented with them (gp/gp_core.py:192-220, 256-261; the mean is
+ * unchanged): block >= m is gp.draw_samples_with_hallucinated_observations(1, Xs, Xh).
+ * jitter_powers_out: optional [k x ceil(m/block)], INT32_MIN = none.                                   */
+int dfh_mo_ts_argmax(dfh_gp* const* gps, int32_t k, int scal,
+                     const double* weights, const double* refs,
+                     const double* Xs, int64_t m, int64_t block,
+                     const double* Xh, int64_t q,            /* hallucinated points, may be NULL / 0 */
+                     const double* U /*[k x m], objective-major*/,
+                     const double* mean_consts, const double* mean_vals,
+                     double* vals_out, double* best_val, int64_t* best_idx,
+                     int32_t* jitter_powers_out /*[k x ceil(m/block)] or NULL*/);
+
 /* ---- candidate generation on the device ---------------------------------------------------
  * The m x d block of uniform candidates every random-search acquisition draws,
  *   np.random.random((max_evals, dim))                   (dragonfly/utils/oper_utils.py:62)
