@@ -21,6 +21,8 @@ GET_L, GET_ALPHA, GET_K = 0, 1, 2
 MO_LIN, MO_TCH, MO_MAX_OBJECTIVES = 0, 1, 8
 FIT_NO_JITTER, FIT_PROJECT_FIRST, FIT_TRY_BEFORE_PROJECT = 1, 2, 4
 LML_X_IS_DEVICE, LML_Y_IS_HOST = 0x100, 0x200       # include/dfhip.h: pointer-kind hints of dfh_gp_lml_batch
+MGPU_LML_FILL, MGPU_LML_SPREAD = 256, 0x1000        # include/dfhip.h: dfh_mgpu_lml_batch's fill rule and its override
+LML_WG_MAX_N = 2047                                 # one workgroup per candidate up to here (csrc/common.h: LMLWG_MAX_N)
 T_NAMES = ['kernmat', 'chol', 'solve', 'cross', 'trsm', 'acq', 'ts', 'spare']
 INT32_MIN = -2**31
 UNIQUE_ID_BYTES = 128
@@ -132,6 +134,10 @@ SIGNATURES = {
   'dfh_mgpu_fit': (C.c_int, [C.c_void_p, C.POINTER(KernelDesc), C.POINTER(C.c_void_p), C.c_int64, C.c_int64,
                              C.POINTER(C.c_void_p), C.c_double, C.c_int, c_double_p, c_int32_p]),
   'dfh_mgpu_free_fit': (C.c_int, [C.c_void_p]),
+  'dfh_lml_shard_plan': (C.c_int, [C.c_int32, C.c_int64, C.c_int, C.c_int, c_int64_p]),
+  'dfh_mgpu_lml_batch': (C.c_int, [C.c_void_p, C.POINTER(KernelDesc), C.c_int32, C.POINTER(C.c_void_p), C.c_int64,
+                                   C.c_int64, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p, c_int64_p]),
   'dfh_mgpu_ts': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_int64_p, C.c_int64, C.POINTER(C.c_void_p),
                             C.c_double, c_double_p, c_int64_p, c_double_p, c_int64_p]),
   'dfh_mgpu_acq_argmax': (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.POINTER(C.c_void_p), c_int64_p,

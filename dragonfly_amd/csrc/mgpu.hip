@@ -23,6 +23,7 @@
 #include <limits.h>
 #include <math.h>
 #include <string.h>
+#include <algorithm>
 #include <mutex>
 #include <thread>
 #include <rccl/rccl.h>      // types only; every call goes through the table below
@@ -406,8 +407,8 @@ namespace {
 // run fn(rank) on one host thread per device (the calls below block on their device's streams);
 // the first failure's status and message are handed to the caller's thread
 template <typename Fn>
-int fan_out(dfh_mgpu* mg, Fn fn) {
-  const int n = mg->n;
+int fan_out(dfh_mgpu* mg, Fn fn, int active = -1) {      // active: only ranks [0, active) take part (default: all)
+  const int n = active < 0 ? mg->n : active;
   std::vector<int> rcs((size_t)n, DFH_OK);
   std::vector<std::string> errs((size_t)n);
   auto work = [&](int r) {
@@ -477,6 +478,49 @@ extern "C" int dfh_mgpu_fit(dfh_mgpu* mg, const dfh_kernel_desc* k, const double
     if (jitter_power) jitter_power[r] = jp;
     return rc;
   });
+}
+
+// How many ranks a tuning batch is cut over, and where (derived, not tuned).  Up to
+// n = LMLWG_MAX_N a candidate is one workgroup and a device holds one workgroup per CU: a second device gets work
+// only once the first is full.  Beyond, a candidate is a full fit that fills a device by itself.
+extern "C" int dfh_lml_shard_plan(int32_t nb, int64_t n, int world, int flags, int64_t* shard_lo) {
+  DFH_ARG(nb >= 0 && n >= 1 && world >= 1 && world <= DFH_MAX_DEVICES && shard_lo);
+  int64_t used = n <= LMLWG_MAX_N ? ((int64_t)nb + DFH_MGPU_LML_FILL - 1) / DFH_MGPU_LML_FILL : (int64_t)nb;
+  if (flags & DFH_MGPU_LML_SPREAD) used = world;
+  used = std::max<int64_t>(1, std::min<int64_t>(used, world));
+  for (int r = 0; r <= world; ++r) shard_lo[r] = nb;
+  for (int r = 0; r < (int)used; ++r) {
+    int64_t hi = 0;
+    DFH_TRY(dfh_shard_bounds(nb, r, (int)used, 1, &shard_lo[r], &hi));
+  }
+  return DFH_OK;
+}
+
+// dfh_gp_lml_batch over contiguous candidate shards: rank r evaluates candidates [shard_lo[r], shard_lo[r + 1]) on its
+// own context from its own host thread and writes its slice of lml_out / jitter_powers itself.  One process owns all
+// the results, so there is nothing to exchange.  Every rank has finished when the call returns, whatever a shard
+// reported; the status is the lowest failing rank's, i.e. that of the shard with the lowest failing candidate.
+extern "C" int dfh_mgpu_lml_batch(dfh_mgpu* mg, const dfh_kernel_desc* descs, int32_t nb, const double* const* X,
+                                  int64_t n, int64_t d, const double* const* y, const double* mean_consts,
+                                  const double* noise_vars, int flags, double* lml_out, int32_t* jitter_powers,
+                                  int64_t* shard_lo) {
+  DFH_ARG(nb >= 0);
+  if (nb == 0) return DFH_OK;
+  DFH_ARG(mg && descs && X && y && noise_vars && lml_out && n >= 1 && d >= 1);
+  for (int r = 0; r < mg->n; ++r) DFH_ARG(X[r] && y[r]);
+  for (int c = 0; c < nb; ++c) DFH_ARG(descs[c].dim == d);
+  std::vector<int64_t> lo((size_t)mg->n + 1, 0);
+  DFH_TRY(dfh_lml_shard_plan(nb, n, mg->n, flags, lo.data()));
+  if (shard_lo) std::copy(lo.begin(), lo.end(), shard_lo);
+  int used = 0;
+  while (used < mg->n && lo[used + 1] > lo[used]) ++used;
+  const int batch_flags = flags & ~DFH_MGPU_LML_SPREAD;
+  return fan_out(mg, [&](int r) -> int {
+    const int64_t a = lo[r];
+    return dfh_gp_lml_batch(mg->ctxs[r], descs + a, (int32_t)(lo[r + 1] - a), X[r], n, d, y[r],
+                            mean_consts ? mean_consts + a : nullptr, noise_vars + a, batch_flags, lml_out + a,
+                            jitter_powers ? jitter_powers + a : nullptr);
+  }, used);
 }
 
 extern "C" int dfh_mgpu_free_fit(dfh_mgpu* mg) {

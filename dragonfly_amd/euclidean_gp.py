@@ -17,6 +17,7 @@ from itertools import product as itertools_product
 import numpy as np
 
 from . import kernel as gp_kernel
+from . import parallel
 from .engine import get_engine
 from .general_utils import map_to_bounds
 from .gp_core import GP, ConstantMean
@@ -219,9 +220,10 @@ class EuclideanGPFitter(object):
 
   _option_specs = euclidean_gp_args
 
-  def __init__(self, X, Y, options=None, reporter=None):
+  def __init__(self, X, Y, options=None, reporter=None, tuning_gpus=None):
     assert len(X) == len(Y)
     self.dim = len(X[0])
+    self.tuning_gpus = tuning_gpus     # N > 1: tuning batches that fill more than one GPU are cut over N (parallel.tuning_route)
     self.reporter = reporter
     self.options = load_options(self._option_specs, partial_options=options)
     self.X = X
@@ -513,6 +515,10 @@ class EuclideanGPFitter(object):
       specs.append(kernel.to_spec(self.dim))
       mean_consts.append(float(mean_const))
       noise_vars.append(float(noise_var))
+    multi = parallel.tuning_route(self.tuning_gpus, len(specs), len(self.X))
+    if multi is not None:
+      Xs = parallel.per_rank_inputs(self, multi, lambda: _as_2d_array(self.X), self.X)
+      return multi.gp_lml_batch(specs, Xs, self.Y, mean_consts, noise_vars)
     return get_engine().gp_lml_batch(specs, self._device_X(), self.Y, mean_consts, noise_vars)
 
   def _optimise_cts_hps_for_given_dscr_hps(self, given_dscr_hps):

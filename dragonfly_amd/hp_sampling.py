@@ -119,10 +119,14 @@ class PosteriorHPSampler(object):
         cts_hp_bounds, dscr_hp_vals, param_order, num_hps, options (post_hp_tune_*),
         lml_batch(cts_list, dscr_list, other_gp_params) -> log marginal likelihoods,
       and, for additive models, add_dim / add_max_group_size.  `sample(num_samples)` returns
-      (cts_hps [num x n_cts], dscr_hps [num x n_dscr], other_gp_params [num]). """
+      (cts_hps [num x n_cts], dscr_hps [num x n_dscr], other_gp_params [num]).
+      tuning_gpus (not None): handed to the fitter, whose lml_batch decides per batch where it runs
+      (parallel.tuning_route); a sampler's batches of a few candidates stay on the fitter's one engine. """
 
-  def __init__(self, fitter, add_dim=None, add_max_group_size=None):
+  def __init__(self, fitter, add_dim=None, add_max_group_size=None, tuning_gpus=None):
     self.f = fitter
+    if tuning_gpus is not None:
+      fitter.tuning_gpus = tuning_gpus
     self.num_cts = len(fitter.cts_hp_bounds)
     self.priors = [UniformPrior(b[0], b[-1]) for b in fitter.cts_hp_bounds] + \
                   [CategoricalPrior(v, np.repeat(1.0 / len(v), len(v))) for v in fitter.dscr_hp_vals]

@@ -52,6 +52,8 @@ edited):
                a time (dragonfly_amd.slice_sampler: the same chain, draw for draw).  Everything
                else of the fitter (options, bounds, priors, the bandit bookkeeping) is the
                reference's code.  install(batched_tuning=False) leaves the fitter alone.
+               install(tuning_gpus=N): a random-search batch that fills more than one GPU is cut over N
+               GPUs of this process (parallel.MultiEngine.gp_lml_batch); smaller batches go where they went.
   S4' MOO      dragonfly.opt.multiobjective_gpb_acquisitions.maximise_acquisition -> ours for
                Euclidean domains: the multi-objective closures are maximised by the batched tree
                search / the vectorised random search too.
@@ -74,8 +76,11 @@ from . import gaplog
 _saved = []     # (object, attribute name, original value)
 
 
-def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, multi_objective=False):
-  """ Rebinds the names listed above; returns the list of patched attributes. """
+def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, multi_objective=False, tuning_gpus=None):
+  """ Rebinds the names listed above; returns the list of patched attributes.
+      tuning_gpus=N > 1 (with batched_tuning): a tuning batch large enough to fill more than one GPU
+      (parallel.lml_shard_plan: more than 256 candidates up to n = 2047) is cut over N GPUs of this process
+      (dfh_mgpu_lml_batch); every other batch, and everything with None or 1, goes exactly where it went before. """
   import dragonfly.gp.kernel as ref_kernel
   import dragonfly.gp.euclidean_gp as ref_egp
   import dragonfly.opt.gpb_acquisitions as ref_acq
@@ -132,13 +137,13 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
   if batched_tuning:
     import dragonfly.opt.gp_bandit as ref_gp_bandit
     import dragonfly.opt.multiobjective_gp_bandit as ref_moo_bandit
-    batched = make_batched_fitter(ref_egp.EuclideanGPFitter)
+    batched = make_batched_fitter(ref_egp.EuclideanGPFitter, tuning_gpus=tuning_gpus)
     _set(ref_gp_bandit, 'EuclideanGPFitter', batched)
     _set(ref_moo_bandit, 'EuclideanGPFitter', batched)
     if cartesian_product:
       # the names the CP bandits construct their fitter by (gp_bandit.py, multiobjective_gp_bandit.py)
       import dragonfly.gp.cartesian_product_gp as ref_cpgp
-      batched_cp = make_batched_cp_fitter(ref_cpgp.CPGPFitter)
+      batched_cp = make_batched_cp_fitter(ref_cpgp.CPGPFitter, tuning_gpus=tuning_gpus)
       _set(ref_gp_bandit, 'CPGPFitter', batched_cp)
       _set(ref_moo_bandit, 'CPGPFitter', batched_cp)
   return patched
@@ -179,9 +184,10 @@ class _KernelMeanNoise(object):
     self.host_kernel = not (hasattr(kernel, 'to_spec') and getattr(kernel, 'has_device_spec', lambda: True)())
 
 
-def make_batched_fitter(ref_fitter_cls):
+def make_batched_fitter(ref_fitter_cls, tuning_gpus=None):
   """ A subclass of the reference's EuclideanGPFitter whose maximum-likelihood tuners evaluate the
-      tuning objective (gp_core.py:551-564) in batches on the device. """
+      tuning objective (gp_core.py:551-564) in batches on the device.  tuning_gpus: see install(). """
+  from . import parallel
   from .doo import pdoo_maximise_batched
   from .engine import get_engine, KernelSpec
   from .gpb_acquisitions import _fortran_direct_available
@@ -191,6 +197,17 @@ def make_batched_fitter(ref_fitter_cls):
   class BatchedEuclideanGPFitter(ref_fitter_cls):
     """ dragonfly.gp.euclidean_gp.EuclideanGPFitter with batched ML tuning (dragonfly_amd.install). """
     pdoo_frontier = 32
+
+    def _engine_lml_batch(self, specs, means, noises):
+      """ one device call for the candidates: the process's engine, or -- install(tuning_gpus=N), a batch that fills
+          more than one GPU -- the candidates cut over N of them """
+      multi = parallel.tuning_route(tuning_gpus, len(specs), len(self.X))
+      if multi is not None:
+        Xs = parallel.per_rank_inputs(self, multi, lambda: _as_2d_array(self.X), self.X)
+        return multi.gp_lml_batch(specs, Xs, self._labels_array(), means, noises)
+      if getattr(self, '_X_dev', None) is None:
+        self._X_dev = get_engine().to_device(_as_2d_array(self.X))
+      return get_engine().gp_lml_batch(specs, self._X_dev, self._labels_array(), means, noises)
 
     def _set_up_ml_hp_tune(self):
       """ gp_core.py:423-474, then the optimisers are swapped for their batch-objective forms
@@ -365,9 +382,7 @@ def make_batched_fitter(ref_fitter_cls):
       decoded = self._decode_candidates(cts_hps_list, dscr_hps, per_cand, other_gp_params)
       if decoded is not None:
         specs, means, noises = decoded
-        if getattr(self, '_X_dev', None) is None:
-          self._X_dev = get_engine().to_device(_as_2d_array(self.X))
-        lmls = get_engine().gp_lml_batch(specs, self._X_dev, self._labels_array(), means, noises)
+        lmls = self._engine_lml_batch(specs, means, noises)
         if gaplog.ENABLED and len(lmls) >= 16:       # (a random-search batch: its arg-max is the fitter's choice)
           gaplog.top2('hp_batch', lmls)
         return lmls
@@ -399,9 +414,7 @@ def make_batched_fitter(ref_fitter_cls):
         return np.array([self._tuning_objective(c, list(dscr_hps[j]) if per_cand else list(dscr_hps),
                                                 other_gp_params=other_gp_params)
                          for j, c in enumerate(cts_hps_list)])
-      if getattr(self, '_X_dev', None) is None:
-        self._X_dev = get_engine().to_device(_as_2d_array(self.X))
-      return get_engine().gp_lml_batch(specs, self._X_dev, self._labels_array(), means, noises)
+      return self._engine_lml_batch(specs, means, noises)
 
     def _labels_array(self):
       """ self.Y as the float64 array every batch call hands to the engine (converted once per list of labels) """
@@ -507,7 +520,7 @@ class _CPKernelMeanNoise(object):
                             all(dists is None for dists in domain_lists_of_dists or []))
 
 
-def make_batched_cp_fitter(ref_fitter_cls):
+def make_batched_cp_fitter(ref_fitter_cls, tuning_gpus=None):
   """ A subclass of the reference's CPGPFitter (gp/cartesian_product_gp.py:322-377) whose maximum-likelihood tuners see
       their objective as a batch: the machinery of make_batched_fitter -- the vectorised random search for 'rand' and
       'rand_exp_sampling', the batched tree search for 'pdoo' and the 'direct' fall-back, the speculative slice sampler
@@ -515,8 +528,9 @@ def make_batched_cp_fitter(ref_fitter_cls):
       through a stand-in for the GP constructor and evaluates the list in ONE dfh_gp_lml_batch call with the
       projection flag.  The points are packed once per data set (the category codes do not depend on the
       hyper-parameters).  Candidates whose kernel has no device description take one fit each. """
+  from . import parallel
   from .engine import get_engine
-  base = make_batched_fitter(ref_fitter_cls)
+  base = make_batched_fitter(ref_fitter_cls, tuning_gpus=tuning_gpus)
 
   class BatchedCPGPFitter(base):
     """ dragonfly.gp.cartesian_product_gp.CPGPFitter with batched ML tuning (dragonfly_amd.install). """
@@ -558,8 +572,13 @@ def make_batched_cp_fitter(ref_fitter_cls):
         return np.array([self._tuning_objective(c, list(dscr_hps[j]) if per_cand else list(dscr_hps),
                                                 other_gp_params=other_gp_params)
                          for j, c in enumerate(cts_hps_list)])
-      lmls = get_engine().gp_lml_batch(specs, self._packed_points(first_kernel), self._labels_array(), means, noises,
-                                       handle_non_psd_kernels=mode)
+      multi = parallel.tuning_route(tuning_gpus, len(specs), len(self.X))
+      if multi is not None:
+        packed = parallel.per_rank_inputs(self, multi, lambda: first_kernel.pack(self.X), self.X)
+        lmls = multi.gp_lml_batch(specs, packed, self._labels_array(), means, noises, handle_non_psd_kernels=mode)
+      else:
+        lmls = get_engine().gp_lml_batch(specs, self._packed_points(first_kernel), self._labels_array(), means, noises,
+                                         handle_non_psd_kernels=mode)
       if gaplog.ENABLED and len(lmls) >= 16:
         gaplog.top2('hp_batch', lmls)
       return lmls
@@ -584,8 +603,9 @@ def make_batched_cp_fitter(ref_fitter_cls):
 
 def uninstall():
   """ Restores every name install() rebound. """
-  from . import gpb_acquisitions
+  from . import gpb_acquisitions, parallel
   for obj, name, old in reversed(_saved):
     setattr(obj, name, old)
   del _saved[:]
+  parallel.close_tuning_engines()
   gpb_acquisitions.external_maximise_with_method = None

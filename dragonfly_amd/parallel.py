@@ -20,6 +20,10 @@ Everything here goes through libdfhip.so (csrc/mgpu.hip: RCCL by dlopen); there 
   * `sharded_*`    -- the shard / evaluate / exchange helpers, written against a communicator
                       object (rank, size, allgather_argmax, allgather_rows) so that the CPU tests
                       can drive them with a stand-in transport.
+
+Hyper-parameter tuning shards the same way: the candidates of a tuning batch are
+independent given (X, y).  `lml_shard_plan` is the cut, `MultiEngine.gp_lml_batch` (dfh_mgpu_lml_batch) and
+`sharded_gp_lml_batch` the two ways to run it, `tuning_route` what the fitters ask (install(tuning_gpus=N)).
 """
 import ctypes as C
 import os
@@ -52,6 +56,27 @@ def reduce_argmax(vals, idxs):
   if bi.value < 0:
     return None, -1
   return float(bv.value), int(bi.value)
+
+
+def lml_shard_plan(nb, n, world, spread=False):
+  """ [(lo, hi)] * world: which candidates of a tuning batch of nb on n observations each of `world` GPUs
+      evaluates (dfh_lml_shard_plan in pure Python; the two must agree, tests/test_mgpu_lml_cpu.py).  Derived, not
+      tuned: up to n = 2047 a candidate is one workgroup and a device holds one per CU, so ceil(nb / 256) ranks take
+      part -- a second GPU gets work only once the first is full; beyond, a candidate is a full fit and every
+      candidate may have a rank of its own.  spread=True cuts over all ranks whatever nb.  The ranks that take part
+      get shard_bounds(nb, r, used); the others, at the tail, get the empty shard (nb, nb). """
+  nb, n, world = int(nb), int(n), int(world)
+  if nb < 0 or n < 1 or world < 1:
+    raise ValueError('lml_shard_plan: need nb >= 0, n >= 1, world >= 1.')
+  used = -(-nb // _lib.MGPU_LML_FILL) if n <= _lib.LML_WG_MAX_N else nb
+  used = max(1, min(world if spread else used, world))
+  per = -(-nb // used)
+  return [(min(r * per, nb), min((r + 1) * per, nb)) if r < used else (nb, nb) for r in range(world)]
+
+
+def lml_ranks_used(plan):
+  """ how many ranks of a plan have candidates """
+  return sum(1 for lo, hi in plan if hi > lo)
 
 
 # ---- passing the RCCL unique id between the processes of one node ---------------------------
@@ -406,6 +431,55 @@ class MultiEngine(object):
       return float(bv.value), int(bi.value), list(zip(list(lv), list(li)))
     return float(bv.value), int(bi.value)
 
+  def to_devices(self, host):
+    """ One copy of a host array in every rank's HBM: [DeviceArray] * size (a fitter uploads its inputs once per
+        data set and hands the list to gp_lml_batch). """
+    return [e.to_device(host) for e in self.engines]
+
+  def gp_lml_batch(self, specs, X, y, mean_consts, noise_vars, allow_jitter=True, return_powers=False,
+                   handle_non_psd_kernels='guaranteed_psd', spread=False, return_shards=False):
+    """ Engine.gp_lml_batch with the candidates cut over the devices (dfh_mgpu_lml_batch; the cut is
+        lml_shard_plan's): rank r's slice of the result is what its Engine returns for those candidates alone.
+        X / y: a host array (shared) or a list with one host array / DeviceArray per rank (to_devices).
+        return_shards: also the cut the library made, [(lo, hi)] * size. """
+    from .engine import DeviceArray, _f64, _psd_flags, _single_kind_descs      # pylint: disable=import-outside-toplevel
+    nb = len(specs)
+    Xs = [x if isinstance(x, DeviceArray) else _f64(x) for x in self._per_rank(X)]
+    ys = [v if isinstance(v, DeviceArray) else _f64(v) for v in self._per_rank(y)]
+    n, d = Xs[0].shape
+    backing = []
+    descs = _single_kind_descs(specs, d, backing)
+    if descs is None:
+      descs = (_lib.KernelDesc * max(nb, 1))()
+      for i, sp in enumerate(specs):
+        one = sp.to_desc()
+        backing.append(one.backing)       # the arrays the copied struct points at
+        descs[i] = one
+    mc = _f64(np.zeros(nb) if mean_consts is None else mean_consts).reshape(-1)
+    nv = _f64(noise_vars).reshape(-1)
+    if len(mc) != nb or len(nv) != nb:
+      raise ValueError('gp_lml_batch: need one mean constant and one noise variance per candidate.')
+    x_dev = [isinstance(x, DeviceArray) for x in Xs]
+    y_dev = [isinstance(v, DeviceArray) for v in ys]
+    if any(x_dev) != all(x_dev) or any(y_dev) != all(y_dev):
+      raise ValueError('gp_lml_batch: per-rank inputs must be all host arrays or all DeviceArrays.')
+    flags = (0 if allow_jitter else _lib.FIT_NO_JITTER) | _psd_flags(handle_non_psd_kernels)
+    flags |= (_lib.LML_X_IS_DEVICE if x_dev[0] else 0) | (0 if y_dev[0] else _lib.LML_Y_IS_HOST)
+    flags |= _lib.MGPU_LML_SPREAD if spread else 0
+    lml = np.empty(nb, dtype=np.float64)
+    jps = np.empty(nb, dtype=np.int32)
+    cut = np.empty(self.size + 1, dtype=np.int64)
+    cut[:] = nb
+    check(self.lib.dfh_mgpu_lml_batch(self.handle, descs, nb, _ptr_array(Xs), n, d, _ptr_array(ys), _engine_ptr(mc),
+                                      _engine_ptr(nv), flags, _engine_ptr(lml), _engine_ptr(jps),
+                                      cut.ctypes.data_as(_lib.c_int64_p)))
+    out = (lml,)
+    if return_powers:
+      out += ([None if p == _lib.INT32_MIN else int(p) for p in jps],)
+    if return_shards:
+      out += ([(int(cut[r]), int(cut[r + 1])) for r in range(self.size)],)
+    return out if len(out) > 1 else lml
+
   def allgather_argmax(self, vals, idxs):
     """ The exchange alone (RCCL all-gather + reduce) for per-rank pairs given by the caller. """
     v = np.ascontiguousarray(vals, dtype=np.float64)
@@ -460,6 +534,78 @@ def sharded_thompson(fitted_gp, cands, U, block, mean_const=0.0, comm=None):
   if world == 1:
     return v, i
   return comm.allgather_argmax(v, i)
+
+
+def sharded_gp_lml_batch(engine, specs, X, y, mean_consts, noise_vars, comm=None, allow_jitter=True,
+                         handle_non_psd_kernels='guaranteed_psd', spread=False):
+  """ The tuning objective of a list of candidates with one process per GPU: this rank's shard (lml_shard_plan) on
+      its own Engine, then every shard's values to every rank -- one allgather_rows per shard, its owner's row
+      travelling.  Returns the lml array of all candidates, identical on every rank.  comm=None: one process. """
+  rank, world = (0, 1) if comm is None else (comm.rank, comm.size)
+  nb = len(specs)
+  plan = lml_shard_plan(nb, X.shape[0] if hasattr(X, 'shape') else len(X), world, spread=spread)
+  lo, hi = plan[rank]
+  mc = np.zeros(nb) if mean_consts is None else np.asarray(mean_consts, dtype=np.float64).reshape(-1)
+  nv = np.asarray(noise_vars, dtype=np.float64).reshape(-1)
+  mine = np.zeros(0)
+  if hi > lo:
+    psd = {} if handle_non_psd_kernels == 'guaranteed_psd' else {'handle_non_psd_kernels': handle_non_psd_kernels}
+    mine = engine.gp_lml_batch(specs[lo:hi], X, y, mc[lo:hi], nv[lo:hi], allow_jitter=allow_jitter, **psd)
+  if world == 1:
+    return np.asarray(mine, dtype=np.float64)
+  out = np.empty(nb, dtype=np.float64)
+  for r, (a, b) in enumerate(plan):
+    for c in range(a, b, _ROW_CHUNK):             # (a row of the device collective holds 4096 doubles, one is the owner's mark)
+      e = min(b, c + _ROW_CHUNK)
+      row = mine[c - lo:e - lo] if r == rank else np.zeros(e - c)
+      out[c:e] = comm.allgather_rows(row, r == rank)
+  return out
+
+
+_ROW_CHUNK = 4095
+
+
+# ---- the fitters' route to several GPUs (install(tuning_gpus=N)) ------------------------------
+_tuning_engines = {}      # world size -> (MultiEngine, created here)
+
+
+def tuning_route(tuning_gpus, nb, n):
+  """ Where a fitter's tuning batch of nb candidates on n observations goes: None -- the process's own Engine,
+      whenever the plan keeps the batch on one rank (tuning_gpus None or 1; every slice-sampler and tree-search
+      call) -- or the MultiEngine(tuning_gpus) of this process, created on the first batch that needs it. """
+  if tuning_gpus is None or int(tuning_gpus) <= 1:
+    return None
+  world = int(tuning_gpus)
+  if lml_ranks_used(lml_shard_plan(nb, n, world)) <= 1:
+    return None
+  if world not in _tuning_engines:
+    _tuning_engines[world] = (MultiEngine(world), True)
+  return _tuning_engines[world][0]
+
+
+def set_tuning_engine(multi, size=None):
+  """ A MultiEngine of the caller's (its devices, its lifetime) as the route of tuning_gpus=multi.size;
+      multi=None forgets the one registered for `size`. """
+  if multi is None:
+    _tuning_engines.pop(int(size), None)
+  else:
+    _tuning_engines[int(multi.size)] = (multi, False)
+
+
+def close_tuning_engines():
+  """ Releases the MultiEngines tuning_route created (install.uninstall) and forgets the registered ones. """
+  for multi, owned in _tuning_engines.values():
+    if owned:
+      multi.close()
+  _tuning_engines.clear()
+
+
+def per_rank_inputs(owner, multi, host_fn, source):
+  """ owner's copy of host_fn() on every rank of `multi`, uploaded once per (multi, source object, length). """
+  cached = getattr(owner, '_amd_multi_inputs', None)
+  if cached is None or cached[0] is not multi or cached[1] is not source or cached[2] != len(source):
+    cached = owner._amd_multi_inputs = (multi, source, len(source), multi.to_devices(host_fn()))      # pylint: disable=protected-access
+  return cached[3]
 
 
 def advance_mt19937(rng, n_doubles):

@@ -476,6 +476,28 @@ int dfh_mgpu_fit(dfh_mgpu* mg, const dfh_kernel_desc* k, const double* const* X,
                  const double* const* y_centred, double noise_var, int flags, double* lml,
                  int32_t* jitter_power);
 int dfh_mgpu_free_fit(dfh_mgpu* mg);
+/* The tuning inner loop over the devices: dfh_gp_lml_batch with the candidates cut into contiguous shards, rank r
+ * evaluating candidates [shard_lo[r], shard_lo[r + 1]) on its own context from its own host thread.  X[r], y[r]: rank
+ * r's copies, as for dfh_mgpu_fit (a host pointer -- the same one may be given for every rank -- or a pointer into
+ * rank r's HBM); descs, mean_consts, noise_vars, flags, lml_out, jitter_powers as for dfh_gp_lml_batch, indexed by the
+ * global candidate number.  The candidates are independent given (X, y): no communicator is involved.
+ * The cut is derived (dfh_lml_shard_plan, host only): up to n = 2047 a candidate is one workgroup and a device runs
+ * DFH_MGPU_LML_FILL of them at a time, so used = min(n_devices, ceil(nb / DFH_MGPU_LML_FILL)) ranks take part -- a
+ * second device gets work only once the first is full; beyond n = 2047 a candidate is a full fit and
+ * used = min(n_devices, nb).  DFH_MGPU_LML_SPREAD in `flags` forces used = n_devices.  Rank r < used takes
+ * dfh_shard_bounds(nb, r, used, 1); the others get an empty shard, no thread and no launch.
+ * Rank r's slice of the result is bit for bit what dfh_gp_lml_batch returns for those candidates alone on that device
+ * (the whole result need not equal ONE single-device call bit for bit: the schedule of a group depends on its size).
+ * Every rank has finished when the call returns, also when a shard failed; the status and message are those of the
+ * lowest failing rank, which holds the lowest-numbered failing candidate's shard.  nb == 0: DFH_OK, no argument is
+ * looked at.  Any other bad argument: DFH_ERR_BAD_ARG before a thread starts.  shard_lo [n_devices + 1] or NULL.      */
+#define DFH_MGPU_LML_FILL   256      /* candidates that fill one device: one workgroup per CU                      */
+#define DFH_MGPU_LML_SPREAD 0x1000   /* cut the batch over every device, however small it is                        */
+int dfh_lml_shard_plan(int32_t nb, int64_t n, int world, int flags, int64_t* shard_lo /* [world + 1] */);
+int dfh_mgpu_lml_batch(dfh_mgpu* mg, const dfh_kernel_desc* descs, int32_t nb, const double* const* X, int64_t n,
+                       int64_t d, const double* const* y, const double* mean_consts, const double* noise_vars,
+                       int flags, double* lml_out /* [nb] */, int32_t* jitter_powers /* [nb] or NULL */,
+                       int64_t* shard_lo /* [n_devices + 1] or NULL */);
 /* dfh_gp_ts / dfh_gp_acq_argmax over contiguous shards: rank r holds rows [off_r, off_r + m[r]) of
  * the global candidate set, off_r = m[0] + ... + m[r-1]; Xs[r] (and U[r], the shard's standard
  * normals) are host pointers or pointers into rank r's HBM; m[r] == 0 is an empty shard.
