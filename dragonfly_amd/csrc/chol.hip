@@ -1721,9 +1721,9 @@ int block_inverse_quality(dfh_ctx* ctx, const double* D, int64_t lda, int64_t nb
 }
 
 int refine_steps(double delta) {
-  static const double tol = []() { const char* e = getenv("DFH_REFINE_TOL"); double v = e ? atof(e) : 1e-13; return v; }();
+  static const double tol = env_double("DFH_REFINE_TOL", 1e-13);
   // test hook (tests/test_gpu_refine_steps.py): every block takes this many steps whatever its inverse is like
-  static const int forced = []() { const char* e = getenv("DFH_REFINE_FORCE_STEPS"); return e ? atoi(e) : -1; }();
+  static const int forced = env_int("DFH_REFINE_FORCE_STEPS", -1);
   if (forced >= 0) return forced > 8 ? 8 : forced;
   if (!(delta > tol)) return 0;
   if (!(delta < 0.25)) return 8;                    // the inverse is barely an inverse: as many steps as we allow
@@ -1769,8 +1769,6 @@ namespace {
 constexpr int LR_REFINE_MAX = 1;   // (each step is two launches on the chain, usually no-ops of ~45 us beside the update)
 const double LR_REFINE_THR[3] = {0.0 /* = the tolerance, filled in at run time */, 3.1622776601683794e-8, 1e-5};
 
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
 }  // namespace
 
 static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda, double* keep_inv,
@@ -1811,11 +1809,11 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
   // One launch per panel (panel_fused_kernel) for single matrices / small batches: n = 4096 2.92 -> 2.50 ms,
   // 8192 8.05 -> 7.07, 16384 34.8 -> 33.4.  Large lock-step batches keep the pivot steps + strips: their
   // workgroups would spend the diagonal chain's 190 us spinning.
-  static const int fused_on = []() { const char* e = getenv("DFH_CHOL_FUSED"); return e ? atoi(e) : 1; }();
+  static const int fused_on = env_int("DFH_CHOL_FUSED", 1);
   // (round 3: lock-step batches of up to 16 gained 5-14 % from it as well, 32 and more lost.  Round 4, with the
   //  transposed panel -- tools/time_lml_batch.py, tools/r4_run18.sh: 32 matrices gain 4 % (n = 3000) to 20 % (n = 600),
   //  64 matrices 7-21 % up to n = 1500 and nothing at n = 3000: up to 32 matrices always, up to 64 while n <= 2048)
-  static const int fused_max_batch_env = []() { const char* e = getenv("DFH_CHOL_FUSED_MAX_BATCH"); return e ? atoi(e) : -1; }();
+  static const int fused_max_batch_env = env_int("DFH_CHOL_FUSED_MAX_BATCH", -1);
   const int fused_max_batch = fused_max_batch_env >= 0 ? fused_max_batch_env : (n <= 2048 ? 64 : 32);
   const bool fused_mode = fused_on && nbatch <= fused_max_batch && !safe;   // safe: no inter-workgroup hand-offs
   static const int fused_prog_sleep = env_int("DFH_CHOL_PROG_SLEEP", 8);
@@ -1824,12 +1822,12 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
   // (64 matrices x 64 workgroups, each re-factoring the pivot block, one workgroup per CU) and the
   // K = 64 panel updates HBM-bound (1.85 GB per step).  A single matrix keeps the pivot-step / GEMM
   // pairs: its chain is bound by launch latency, which the strips do not shorten.
-  static const int strips_on = []() { const char* e = getenv("DFH_CHOL_STRIPS"); return e ? atoi(e) : 1; }();
-  static const int strips_max_wg = []() { const char* e = getenv("DFH_CHOL_STRIPS_MAX_WG"); return e ? atoi(e) : (1 << 30); }();
+  static const int strips_on = env_int("DFH_CHOL_STRIPS", 1);
+  static const int strips_max_wg = env_int("DFH_CHOL_STRIPS_MAX_WG", 1 << 30);
   // from how many row strips on: 129 in a lock-step batch (round 3, tools/prof_lml.py: 20 - 64 matrices of
   // n = 600 ... 2000 gain 5 - 20 % over the 513 of round 2; below ~100 strips the pivot steps win), 513 for a
   // single matrix (which takes the one-launch panel anyway unless that is switched off)
-  static const int strips_min_env = []() { const char* e = getenv("DFH_CHOL_STRIPS_MIN_WG"); return e ? atoi(e) : -1; }();
+  static const int strips_min_env = env_int("DFH_CHOL_STRIPS_MIN_WG", -1);
   const int strips_min_wg = strips_min_env >= 0 ? strips_min_env : (nbatch > 1 ? 129 : 513);
   double* T = nullptr;
   if (keep_inv) DFH_TRY(scratch_get(ctx, SCR_CHOLT, (size_t)nbatch * strideT * 8, (void**)&T));
@@ -1854,8 +1852,8 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
     attr_set = true;
   }
   const int64_t nblk = (n + NB - 1) / NB;
-  static const bool pair_on = []() { const char* e = getenv("DFH_CHOL_PAIR"); return e ? atoi(e) != 0 : true; }();
-  static const long pair_min_rem = []() { const char* e = getenv("DFH_CHOL_PAIR_MIN_REM"); return e ? atol(e) : 6144L; }();
+  static const bool pair_on = env_flag("DFH_CHOL_PAIR", true);
+  static const long pair_min_rem = env_long("DFH_CHOL_PAIR_MIN_REM", 6144L);
 
   // ---- resident look-ahead: which panels, and what it needs (nothing may allocate inside the loop:
   //      hipMalloc can wait for the device, and a gate kernel may be waiting for a launch not yet enqueued) ----
@@ -1874,7 +1872,7 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
     DFH_TRY(scratch_get(ctx, SCR_CHOLX, (size_t)2 * lr_xstride * 8, (void**)&lr_X));
     DFH_TRY(scratch_get(ctx, SCR_CHOLR, (size_t)(n - NB) * NB * 8, (void**)&lr_R));
   }
-  static const double refine_tol = []() { const char* e = getenv("DFH_REFINE_TOL"); return e ? atof(e) : 1e-13; }();
+  static const double refine_tol = env_double("DFH_REFINE_TOL", 1e-13);
   hipEvent_t ev_start, ev_done;
   DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 0, &ev_start));
   DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 1, &ev_done));
@@ -2184,6 +2182,51 @@ int cholesky_device(dfh_ctx* ctx, double* A, int64_t n, int64_t lda, double* kee
   DFH_TRY((*rebuild)());
   rc = attempt(false, true);
   return (rc == DFH_INTERNAL_RETRY || rc == DFH_INTERNAL_RETRY_COND) ? DFH_ERR_HIP : rc;
+}
+
+static int ladder_pow(int p, double max_M, double* out) {
+  *out = pow(10.0, (double)p) * max_M;      // (10 ** diag_noise_power) * max_M, general_utils.py:189
+  return DFH_OK;
+}
+
+// factor dL (holding M) in place with the stable_cholesky ladder; M is re-created by `rebuild`
+// when a retry is needed (the failed factorisation destroys it).
+int stable_cholesky_device(dfh_ctx* ctx, double* dL, int64_t n, double* keep_inv, bool allow_jitter,
+                           const std::function<int()>& rebuild, int32_t* jitter_power, double* jitter_added,
+                           int64_t ld, int* refine_out) {
+  if (ld == 0) ld = n;
+  if (jitter_power) *jitter_power = INT32_MIN;
+  if (jitter_added) *jitter_added = 0.0;
+  int64_t piv = 0;
+  int rc = cholesky_device(ctx, dL, n, ld, keep_inv, &piv, 1, 0, 0, refine_out, false, &rebuild);
+  if (rc != DFH_ERR_NOT_PD || !allow_jitter) return rc;
+  // general_utils.py:183-203
+  DFH_TRY(rebuild());
+  double max_M = 0.0;
+  DFH_TRY(diag_max(ctx, dL, n, ld, &max_M));
+  bool first = true;
+  for (int p = -11; p < 5; ++p) {
+    double diag_noise;
+    ladder_pow(p, max_M, &diag_noise);
+    if (!first) DFH_TRY(rebuild());
+    first = false;
+    DFH_TRY(add_diag(ctx, dL, n, ld, diag_noise));      // M + diag_noise * np.eye(n)
+    const std::function<int()> rebuild_jit = [&]() -> int { DFH_TRY(rebuild()); return add_diag(ctx, dL, n, ld, diag_noise); };
+    rc = cholesky_device(ctx, dL, n, ld, keep_inv, &piv, 1, 0, 0, refine_out, false, &rebuild_jit);
+    if (rc == DFH_OK) {
+      if (jitter_power) *jitter_power = p;
+      if (jitter_added) *jitter_added = diag_noise;
+      return DFH_OK;
+    }
+    if (rc != DFH_ERR_NOT_PD) return rc;
+    if (p + 1 >= 5) {
+      dfh_set_error("Could not compute Cholesky decomposition despite adding %0.4f to the diagonal. "
+                    "This is likely because the M is not positive semi-definite or has infinities/nans.",
+                    diag_noise);
+      return DFH_ERR_JITTER;
+    }
+  }
+  return DFH_ERR_JITTER;
 }
 
 // Right-looking block substitution: once x_i is final it is pushed into every remaining row

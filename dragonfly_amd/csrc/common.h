@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
+#include <math.h>
 #include <string>
 #include <vector>
 #include <unordered_map>
@@ -38,6 +40,14 @@ void dfh_set_error(const char* fmt, ...);
   } while (0)
 
 #define DFH_LAUNCH_CHECK() DFH_HIP(hipGetLastError())
+
+// Run-time switches: the value of an environment variable, or dflt when it is not set.  A site keeps
+// the result in a `static const` (one read per process) and writes its own clamp, if it has one, next to the call.
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline long env_long(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
+static_assert(sizeof(long) == sizeof(int64_t), "env_long also reads the 64-bit switches");
+inline double env_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }
+inline bool env_flag(const char* name, bool dflt) { const char* e = getenv(name); return e ? atoi(e) != 0 : dflt; }
 
 // A device allocation that is kept for the life of its owner (ctx scratch or gp state).
 struct DevBuf {
@@ -368,6 +378,13 @@ int cholesky_device(dfh_ctx* ctx, double* A, int64_t n, int64_t lda, double* kee
                     int64_t* info_pivot, int nbatch = 1, int64_t strideA = 0, int64_t strideKeep = 0,
                     int* refine_out = nullptr, bool inv64_only = false,
                     const std::function<int()>* rebuild = nullptr);
+// A in place -> its factor under the stable_cholesky ladder (general_utils.py:166-203): plain Cholesky first; if that
+// fails and allow_jitter, 10^-11 .. 10^4 times the largest diagonal entry is added until it factors.  `rebuild`
+// re-creates the matrix in A (a failed factorisation destroys it).  *jitter_power: the power that was needed
+// (INT32_MIN: none), *jitter_added: what went onto the diagonal.  ld = 0: n.
+int stable_cholesky_device(dfh_ctx* ctx, double* A, int64_t n, double* keep_inv, bool allow_jitter,
+                           const std::function<int()>& rebuild, int32_t* jitter_power, double* jitter_added,
+                           int64_t ld = 0, int* refine_out = nullptr);
 constexpr int DFH_INTERNAL_RETRY = 1000;   // chol.hip internal: never crosses the C-ABI (a hand-off wait expired)
 constexpr int DFH_INTERNAL_RETRY_COND = 1001;   // ... a block inverse too poor for the inverse-based panel solve (deterministic)
 
@@ -429,3 +446,9 @@ int logdet_and_dot_device(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl,
                           const double* b, double* d_out2);
 int logdet_and_dot(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const double* a,
                    const double* b, double* host_logdet, double* host_dot);
+// log marginal likelihood from logdet = sum(log L_ii) and dot = (y - m)^T alpha      (gp_core.py:224-226)
+inline double lml_value(double logdet, double dot, int64_t n) {
+  return -0.5 * dot - logdet - 0.5 * (double)n * log(2.0 * M_PI);
+}
+// the projection branches of _get_cholesky_decomp (gp_core.py:827-841) among the fit flags
+constexpr int DFH_FIT_PSD_FLAGS = DFH_FIT_PROJECT_FIRST | DFH_FIT_TRY_BEFORE_PROJECT;

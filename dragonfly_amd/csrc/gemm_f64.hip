@@ -672,7 +672,7 @@ int gemm_f64(dfh_ctx* ctx, int flags, int64_t M, int64_t N, int64_t K, double al
   ext.cond = ctx->gemm_cond; ext.cond_thr = ctx->gemm_cond_thr; ext.la_cnt = ctx->gemm_la_cnt; ext.la_pad = 0; ext.vgrid = 0;
   // diagnostics (tools/chol_gemm_prof.py): DFH_GEMM_FORCE_LA=1 sends every eligible LOWER product through the
   // look-ahead tile order (counters in scratch) so that the extended kernel can be timed on its own
-  static const bool force_la = getenv("DFH_GEMM_FORCE_LA") && atoi(getenv("DFH_GEMM_FORCE_LA")) != 0;
+  static const bool force_la = env_flag("DFH_GEMM_FORCE_LA", false);
   if (force_la && !ext.la_cnt && (flags & GEMM_LOWER) && !batch && M >= 5 * 128) {
     int* dummy = nullptr;
     DFH_TRY(scratch_get(ctx, SCR_RED, 64, (void**)&dummy));

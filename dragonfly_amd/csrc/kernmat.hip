@@ -808,7 +808,7 @@ int launch_strip(dfh_ctx* ctx, KmArgs a, int C) {
   const long strips = ((long)a.n1 + 31) / 32;
   const int tile_cols = (C >= 6 || a.mu_part) ? 32 : 64;
   const long ntile = ((long)a.n2 + tile_cols - 1) / tile_cols;
-  static const long want_waves = []() { const char* e = getenv("DFH_KM_WAVES"); long v = e ? atol(e) : 8192; return v > 0 ? v : 8192; }();
+  static const long waves_env = env_long("DFH_KM_WAVES", 8192), want_waves = waves_env > 0 ? waves_env : 8192;
   long segs = (want_waves + strips - 1) / strips;
   if (segs > ntile) segs = ntile;
   if (segs < 1) segs = 1;
@@ -1498,7 +1498,7 @@ int lml_tiny_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double* dX
   // the device: a few hundred bytes over PCIe) and writes its four numbers per candidate straight back into it, status
   // word last, while the host polls that word -- one launch, no copy, no stream synchronisation.  DFH_LML_DIRECT=0: off;
   // =N: groups of up to N candidates (default 16).
-  static const int direct_max = []() { const char* e = getenv("DFH_LML_DIRECT"); return e ? atoi(e) : 16; }();
+  static const int direct_max = env_int("DFH_LML_DIRECT", 16);
   const bool direct = count <= direct_max && at <= (size_t)32768 && !ctx->timing;
   void* d_blob = nullptr;
   double* d_out = nullptr;
@@ -1533,7 +1533,7 @@ int lml_tiny_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double* dX
     attr_set[ctx->device] = true;
   }
   // n <= 63: the system is one 64 x 64 tile for the barrier-free factorisation (k_lml_tiny64); DFH_LML_TINY64=0: k_lml_tiny
-  static const bool tiny64 = []() { const char* e = getenv("DFH_LML_TINY64"); return e ? atoi(e) != 0 : true; }();
+  static const bool tiny64 = env_flag("DFH_LML_TINY64", true);
   if (tiny64 && n <= TINY64_MAX_N) {
     const size_t lds_bytes = TINY64_FIXED_LDS + sizeof(double) * ((size_t)n * Pmax + (size_t)n * parts_max);
     hipLaunchKernelGGL(k_lml_tiny64, dim3((unsigned)count), dim3(256), lds_bytes, ctx->stream, a);
@@ -1908,7 +1908,7 @@ int pack_scaled(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bool 
   DFH_ARG(!pre_gathered || part_hi == part_lo + 1);
   const int c_lo = kd.parts[part_lo].poff;
   const int c_hi = kd.parts[part_hi - 1].poff + kd.parts[part_hi - 1].kc;
-  static const bool fused_pack = getenv("DFH_PACK_FUSED") ? atoi(getenv("DFH_PACK_FUSED")) != 0 : true;
+  static const bool fused_pack = env_flag("DFH_PACK_FUSED", true);
   if (fused_pack && c_hi - c_lo <= 2048) {
     const int w = c_hi - c_lo;
     int R = 4096 / w;                          // <= 32 KB of LDS
@@ -2160,7 +2160,7 @@ int kernmat_packed(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bo
   a.lower_only = (symmetric && ctx->km_lower_only) ? 1 : 0;
   a.K = K; a.ldk = ldk;
   {
-    static const int nt_env = []() { const char* e = getenv("DFH_KM_NT"); return e ? atoi(e) : -1; }();
+    static const int nt_env = env_int("DFH_KM_NT", -1);
     a.nt_stores = nt_env >= 0 ? (nt_env != 0) : (kd.P >= 16 && n1 * n2 >= (int64_t)4096 * 4096);
   }
   const bool multi = kd.multi;
@@ -2189,7 +2189,7 @@ int kernmat_packed(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bo
       (n1 + 63) / 64 <= 65535) {
     // 64 x 64 tiles, 16-column operand chunks, 32-row staging: ~20 KB of LDS and 69 VGPRs per
     // workgroup -> 7-8 workgroups per CU whose load / MFMA / exp / store phases overlap.
-    static const int sym_cfg = []() { const char* e = getenv("DFH_KM_CFG"); return e ? atoi(e) : 0; }();
+    static const int sym_cfg = env_int("DFH_KM_CFG", 0);
     auto smem_bytes = [](int TS, int KC, int SR) {
       const int oper = 2 * TS * (KC + 2), stage = SR * (TS + 2);
       return ((oper > stage ? oper : stage) + 2 * TS) * 8;
@@ -2210,13 +2210,13 @@ int kernmat_packed(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bo
       }
     } else {
       // strip kernel: SE / Matern (nu = 0.5, 1.5, 2.5), packed width 8 / 16 / 24 / 32, 32-bit in-strip offsets
-      static const bool strip_on = []() { const char* e = getenv("DFH_KM_STRIP"); return e ? atoi(e) != 0 : true; }();
+      static const bool strip_on = env_flag("DFH_KM_STRIP", true);
       const PartDev& hp = kd.parts[part_lo];
       const bool strip_ok = strip_on && (hp.kind == DFH_KERNEL_SE || (hp.kind == DFH_KERNEL_MATERN && hp.p <= 2)) &&
                             hp.kc >= 8 && hp.kc <= 32 && hp.kc % 8 == 0 && kd.P % 2 == 0 && hp.poff % 2 == 0 &&
                             32 * ldk + 64 < (1LL << 31) && (n1 + 127) / 128 <= 65535 &&
                             (reinterpret_cast<uintptr_t>(Xp1) & 15) == 0 && (reinterpret_cast<uintptr_t>(Xp2) & 15) == 0;
-      static const bool mu_fused = []() { const char* e = getenv("DFH_KM_FUSED_MEAN"); return e ? atoi(e) != 0 : true; }();
+      static const bool mu_fused = env_flag("DFH_KM_FUSED_MEAN", true);
       if (strip_ok && mu_fused && mu_alpha && mu_out && mu_done) {
         a.mu_nblk = (int)((n2 + KM_MU_BLOCK - 1) / KM_MU_BLOCK);
         DFH_TRY(scratch_get(ctx, SCR_MUPART, (size_t)n1 * a.mu_nblk * 8, (void**)&a.mu_part));
@@ -2241,7 +2241,7 @@ int kernmat_packed(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bo
   if (multi && symmetric && kd.stationary && !kd.nested && (ldk & 1) == 0 && (reinterpret_cast<uintptr_t>(K) & 15) == 0 &&
       (n1 + 63) / 64 <= 65535 && kd.P % 2 == 0 && (reinterpret_cast<uintptr_t>(Xp1) & 15) == 0) {
     // symmetric Gram of an additive / product kernel: lower-triangle tiles, parts adjacent and <= 16 columns wide
-    static const bool symmulti_on = []() { const char* e = getenv("DFH_KM_SYMMULTI"); return e ? atoi(e) != 0 : true; }();
+    static const bool symmulti_on = env_flag("DFH_KM_SYMMULTI", true);
     bool ok = symmulti_on;
     for (int g = part_lo; g < part_hi && ok; ++g) {
       ok = kd.parts[g].kc <= 16 && kd.parts[g].poff % 2 == 0 &&

@@ -144,7 +144,7 @@ int psd_project_device(dfh_ctx* ctx, const double* M, int64_t n, int64_t ldm, do
       return DFH_ERR_NOT_PD;
     }
   }
-  static const bool early_stop = []() { const char* e = getenv("DFH_PSD_EARLY_STOP"); return e ? atoi(e) != 0 : true; }();
+  static const bool early_stop = env_flag("DFH_PSD_EARLY_STOP", true);
   for (int it = 0; it < PSD_ITERS; ++it) {
     // T = X X^T (= X^2, X symmetric) on the lower triangle; T <- 3 I - T, mirrored
     DFH_TRY(gemm_f64(ctx, GEMM_LOWER, n, n, n, 1.0, Xc, n, Xc, n, 0.0, nullptr, 0, T, n));

@@ -422,7 +422,8 @@ extern "C" int dfh_rand_mt19937_uniform(dfh_ctx* ctx, uint32_t* key, int32_t* po
   // The words before and after the shard are not walked when there are many of them: the state
   // jumps over them on the host (mtjump.hip; a few ms whatever the distance, the walk is 0.36 us per
   // 624 words).  DFH_MT_JUMP_MIN_WORDS moves the threshold (0: never jump).
-  static const int64_t jump_min = getenv("DFH_MT_JUMP_MIN_WORDS") ? atoll(getenv("DFH_MT_JUMP_MIN_WORDS")) : (int64_t(1) << 23);
+  // (read with atol where it was atoll: long is 64 bits here, common.h asserts it)
+  static const int64_t jump_min = env_long("DFH_MT_JUMP_MIN_WORDS", 1L << 23);
   const bool jump_front = jump_min > 0 && keep_lo >= jump_min;
   const bool jump_back = jump_min > 0 && total_words - keep_hi >= jump_min;
   const int64_t walk_lo = jump_front ? keep_lo : 0, walk_hi = jump_back ? keep_hi : total_words;
