@@ -22,6 +22,7 @@ def relerr(a, b):
 
 
 def stage_gemm():
+  """ A quick look at dfh_gemm by hand; the checked cases, variant by variant, are tests/test_gpu_gemm.py. """
   from dragonfly_amd.engine import Engine
   eng = Engine()
   print(eng.name())
