@@ -1,8 +1,9 @@
-// Blocked right-looking Cholesky + the triangular solves built on its diagonal-block inverses.
+// Blocked right-looking Cholesky and the inverses of its diagonal blocks (the triangular solves built on them are
+// trsolve.hip; the one-workgroup tuning objective, which shares the 64 x 64 machinery of factor64.h, is lml_wg.h,
+// compiled as part of this unit).
 //
-// Replaces np.linalg.cholesky (LAPACK dpotrf) at dragonfly/utils/general_utils.py:178,190 and
-// scipy.linalg.solve_triangular (dtrtrs) at general_utils.py:213 as used by
-// GP.build_posterior / GP.eval (dragonfly/gp/gp_core.py:159-163,180).
+// Replaces np.linalg.cholesky (LAPACK dpotrf) at dragonfly/utils/general_utils.py:178,190 as used by
+// GP.build_posterior (dragonfly/gp/gp_core.py:159-160).
 //
 // Structure (row-major lower, n x n):
 //   outer panels of CHOL_NB = 512 columns; inside a panel the 512 x 512 diagonal block is
@@ -13,8 +14,8 @@
 //   levels of batched GEMMs ([[A,0],[B,C]]^-1 = [[A^-1,0],[-C^-1 B A^-1, C^-1]]), so the panel
 //   solve  L21 = A21 L11^-T  and the trailing update  A22 -= L21 L21^T  are two large MFMA_F64
 //   GEMMs -- where n^3/3 of the flops are.  The 512-block inverses are kept: the posterior
-//   solve (trsm_rows) and the alpha solves (trsv_*) reuse them, which turns every triangular
-//   solve on the hot path into GEMM / GEMV work.
+//   solve (trsm_rows) and the alpha solves (trsv_*) of trsolve.hip reuse them, which turns every
+//   triangular solve on the hot path into GEMM / GEMV work.
 #include "common.h"
 #include <cmath>
 #include <functional>
@@ -24,17 +25,7 @@
 
 namespace {
 
-constexpr int PBP = 65;      // LDS row stride
-
-// Hand-off status word of a factorisation (d_info[CHOL_MAX_BATCH + 8], zeroed per call): set when a
-// bounded wait expired.  The host then repeats the factorisation on the schedule without
-// inter-workgroup hand-offs (cholesky_device), or reports DFH_ERR_HIP when the input is gone.
-constexpr unsigned SYNC_ST_FUSED = 2;     // a strip of the one-launch panel waited too long for another strip
-constexpr unsigned SYNC_ST_GATE = 4;      // a gate kernel / resident diagonal kernel waited too long for another launch
-constexpr int SPIN_LIMIT_DEFAULT = 1 << 21;   // polls of ~0.5 us each: a second, a few hundred times the longest legitimate wait
-
-#include "factor64.h"   // factor64_waves and its helpers (PB, SYNC_ST_RING, fast_rcp, perm16, quad_sum, ...)
-#include "kerneval.h"   // kernel evaluation (the fused tuning objective builds its Gram matrix itself)
+#include "factor64.h"   // factor64_waves and its helpers (PB, PBP, SPP, SYNC_ST_*, fast_rcp, perm16, quad_sum, ...)
 
 // One 64-wide step of the diagonal-block factorisation, one launch:
 //   workgroup 0     : factors the nb x nb pivot block at D and writes the factor to Lout;
@@ -42,7 +33,6 @@ constexpr int SPIN_LIMIT_DEFAULT = 1 << 21;   // polls of ~0.5 us each: a second
 //                     hand-off needed) and solves 64 rows of the column below it,
 //                     P[r,:] <- P[r,:] L^-T, by forward substitution with four lanes per row.
 // info[0] <- pivot_base + j + 1 for the first non-positive / NaN pivot.
-constexpr int SPP = 66;      // row stride of the column-permuted factor image (16-byte aligned rows)
 __global__ __launch_bounds__(256) void diag_step64_kernel(double* __restrict__ D, long lda, int nb,
                                                           int rows_below, long pivot_base,
                                                           long long* info, double* __restrict__ Lout,
@@ -188,707 +178,12 @@ __global__ __launch_bounds__(256) void diag_step64_kernel(double* __restrict__ D
   }
   if (info_dbg[7] != 0 && tid == 0 && blockIdx.x == gridDim.x - 1 && blockIdx.y == 0) info_dbg[4] = (long long)(__builtin_amdgcn_s_memtime() - t2);
 }
-static_assert(SPP == SPP_STAGE, "staging stride");
-constexpr int DIAG_STEP_SMEM = (PB * SPP + PB * PBP + PB + PB * PB + 3 * PB * 17 + 8 * 16 * 17) * 8;   // image, panel rows, rdiag, ring, layout buffers, 16-blocks + inverses
 
-// ---------------------------------------------------------------------------------------------
-// The whole tuning objective of one hyper-parameter candidate in ONE workgroup (round 5): Cholesky
-// factor of the candidate's (n + 1) x (n + 1) AUGMENTED matrix
-//     [ K + s2 I   . ]        L_aug = [ L    0 ]      z = L^-1 (y - m)
-//     [ (y - m)^T  c ]                [ z^T  * ]
-// so that the forward solve of GP.build_posterior (gp_core.py:161-162) is finished when the factor is
-// -- the log marginal likelihood (gp_core.py:222-227) needs sum(log L_ii) and z.z only.  Replaces, for
-// 128 < n <= 2047 and lock-step groups of candidates (GPFitter._tuning_objective, gp_core.py:551-574),
-// the batched schedule of cholesky_device: at n = 1000 x 64 that was 44 launches, two one-launch panels
-// whose 1024 workgroups queue for 256 CUs, and 1.1 ms of 512-block inverses the likelihood never uses
-// (profiles/r05_lml_batch_before.txt).  Here a candidate never leaves its CU:
-//   left-looking over 64-column blocks j:  T_ij = A_ij - sum_{k<j} L_ik L_jk^T for the tile rows i >= j,
-//   two tile rows at a time (each wave owns 16 rows of every tile: its A operand goes straight from L2 / HBM
-//   into MFMA fragments, the B operand -- block row j, shared by the four waves -- through a double-buffered
-//   LDS image; lmlwg_gemm); then the diagonal tile through factor64_waves and the tiles below it through the
-//   16-column MFMA substitution of diag_step64_kernel; every tile of A is read once, every tile of L written once.
-// The matrix is stored padded to NP = 64 ceil((n + 1) / 64) rows and columns; rows beyond n are not read
-// from memory but generated (row n: y - m and the diagonal entry c = 1 + |y - m|^2 / s2 > z.z, rows
-// beyond: identity), so the Gram kernel only has to fill the n x n part.
-// One workgroup per CU (the factor64_waves / substitution LDS images take 141 KB): the latency-bound
-// diagonal steps are NOT hidden behind another candidate's products -- the price of never waiting for
-// another workgroup.
-struct LmlWgArgs {
-  double* K; long sK; long ld;      // padded matrices, sK doubles apart, row stride ld
-  int n, nbt;                       // observations; tile rows = ceil((n + 1) / 64)
-  const double* y;                  // [n]
-  const double* par;                // [count] augmented diagonal entry c, then [count] prior mean m
-  int count;
-  double* out2;                     // [count][2]: sum(log L_ii), z.z
-  long long* info;                  // [count]: 1-based index of the first failing pivot (0: none)
-  // lml_team_kernel only
-  int T;                            // workgroups per candidate
-  int* sync;                        // [count][LMLT_SYNC_INTS], zeroed per launch: diag[j], then brow[j] (see the kernel)
-  double* linvbuf;                  // [count][nbt][LMLT_LINV]: inverses of the diagonal tiles' 16 x 16 blocks, handed on
-  unsigned long long* status;       // hand-off status word (SYNC_ST_*)
-  int spin_limit;
-#ifdef DFH_DEBUG_HOOKS
-  long long* stamps = nullptr;      // dfh_debug_lmlt_stamps: [workgroup][32 columns][16] s_memrealtime (100 MHz) at the LSTAMP points
-#endif
-};
-constexpr int LMLT_SYNC_INTS = 64, LMLT_LINV = 4 * 16 * 17;
-#ifdef DFH_DEBUG_HOOKS
-#define LSTAMP(a, j, e) do { if ((a).stamps && threadIdx.x == 0) (a).stamps[((long)blockIdx.x * 32 + (j)) * 16 + (e)] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
-long long* g_lmlt_stamps = nullptr;
-#else
-#define LSTAMP(a, j, e) do {} while (0)
-#endif
+}  // namespace
 
-// this wave's 16 x 64 slice of tile (i, j), as MFMA accumulators: acc[t][r] = element (64 i + 16 w + kq + 4 r, 64 j + 16 t + l15)
-__device__ __forceinline__ void lmlwg_load_tile(const LmlWgArgs& a, const double* __restrict__ Km, double mean, double cdiag,
-                                                int i, int j, int w, int kq, int l15, double4_t (&acc)[4]) {
-  const int n = a.n;
-  const long ld = a.ld;
-  if (64 * (i + 1) <= n) {                             // (uniform) every row of the tile is a row of K
-    const double* p = Km + (long)(64 * i + 16 * w + kq) * ld + 64 * j + l15;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[t][r] = p[(long)(4 * r) * ld + 16 * t];
-  } else {
-    // (unconditional loads from clamped addresses, then selects: a load under a condition is waited for on the
-    //  spot, and sixteen memory latencies in a row per tile were a tenth of the kernel's time)
-    double kv[4][4], yv[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int gj = min(64 * j + 16 * t + l15, n - 1);
-      yv[t] = a.y[gj];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) kv[t][r] = Km[(long)min(64 * i + 16 * w + kq + 4 * r, n - 1) * ld + gj];
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int gi = 64 * i + 16 * w + kq + 4 * r, gj = 64 * j + 16 * t + l15;
-        const double on_row_n = (gj < n) ? yv[t] - mean : (gj == n ? cdiag : 0.0);
-        const double in_k = (gj < n) ? kv[t][r] : 0.0;
-        acc[t][r] = (gi < n) ? in_k : (gi == n ? on_row_n : (gi == gj ? 1.0 : 0.0));
-      }
-  }
-}
+#include "lml_wg.h"   // the one-workgroup / team tuning objective: its own file, this translation unit (see there for why)
 
-// acc[q] += L[tile row i0 + q * istep][0 : 64 j] L[tile row brow][0 : 64 j]^T for q < RG, this wave's 16 rows of each
-// tile (brow: j, or j + 1 for the look-ahead product of the next diagonal tile).  Sixteen columns per step.
-//   A operand (this wave's own rows): straight from L2 / HBM into MFMA fragments -- lane (kq, l15) holds columns
-//     2 kq, 2 kq + 1 and 8 + 2 kq, 9 + 2 kq of its row (two 16-byte loads, 64 contiguous bytes per row and
-//     instruction) and the four MFMAs of a step contract over the columns {c, 2 + c, 4 + c, 6 + c} + {0, 8}: any
-//     assignment of columns to k-slots is a valid product as long as both operands use the same one.
-//   B operand (the 64 rows of tile row brow, the same for all four waves): through a double-buffered LDS image
-//     Bs[2][64][LG_BKP], 32 bytes per thread and step, one barrier per step.  (Round 5's first version had every
-//     wave load all of B itself: ten loads per sixteen MFMAs at one tile row per wave, and the products ran at a
-//     third of the matrix pipe's rate -- tools/dbg_lmlt.py.)
-// Loads are issued NS steps ahead and unconditionally (a load under a condition makes the compiler drain the whole
-// queue -- s_waitcnt vmcnt(0) -- before every step; the last steps therefore re-load the final step's operands).
-// Called by all four waves together (barriers inside); ends behind a barrier: Bs is free again.
-constexpr int LG_BKP = 18;                             // row stride of the B image (doubles): 16-byte aligned rows
-template <int RG>
-__device__ __forceinline__ void lmlwg_gemm(const double* __restrict__ Km, long ld, int j, int i0, int w, int kq, int l15,
-                                           double4_t (&acc)[2][4], double* Bs, int istep = 1, int brow = -1) {
-  const int nch = 4 * j;                               // (a multiple of NS)
-  if (nch <= 0) return;
-  if (brow < 0) brow = j;
-  const int tid = threadIdx.x;
-  const double* pa[RG];
-#pragma unroll
-  for (int q = 0; q < RG; ++q) pa[q] = Km + (long)(64 * (i0 + q * istep) + 16 * w + l15) * ld + 2 * kq;
-  const double* pbg = Km + (long)(64 * brow + (tid >> 2)) * ld + 4 * (tid & 3);   // staging: row tid / 4, four columns
-  double* bst = Bs + (tid >> 2) * LG_BKP + 4 * (tid & 3);
-  const double* bfr = Bs + l15 * LG_BKP + 2 * kq;      // fragments: row 16 t + l15, columns 2 kq (+ 8)
-  constexpr int NS = 4;
-  double2_t fa[NS][RG][2], gb[NS][2];
-  auto load_a = [&](int c, double2_t (&xa)[RG][2]) {
-#pragma unroll
-    for (int q = 0; q < RG; ++q) {
-      xa[q][0] = *reinterpret_cast<const double2_t*>(pa[q] + 16 * c);
-      xa[q][1] = *reinterpret_cast<const double2_t*>(pa[q] + 16 * c + 8);
-    }
-  };
-  auto load_b = [&](int c, double2_t (&xb)[2]) {
-    xb[0] = *reinterpret_cast<const double2_t*>(pbg + 16 * c);
-    xb[1] = *reinterpret_cast<const double2_t*>(pbg + 16 * c + 2);
-  };
-  auto stage_b = [&](const double2_t (&xb)[2], int buf) {
-    *reinterpret_cast<double2_t*>(bst + buf * (64 * LG_BKP)) = xb[0];
-    *reinterpret_cast<double2_t*>(bst + buf * (64 * LG_BKP) + 2) = xb[1];
-  };
-  auto mma = [&](const double2_t (&xa)[RG][2], int buf) {
-    double2_t xb[4][2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      xb[t][0] = *reinterpret_cast<const double2_t*>(bfr + buf * (64 * LG_BKP) + 16 * t * LG_BKP);
-      xb[t][1] = *reinterpret_cast<const double2_t*>(bfr + buf * (64 * LG_BKP) + 16 * t * LG_BKP + 8);
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int q = 0; q < RG; ++q)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const double av = (s & 1) ? xa[q][s >> 1].y : xa[q][s >> 1].x;
-          const double bv = (s & 1) ? xb[t][s >> 1].y : xb[t][s >> 1].x;
-          acc[q][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[q][t], 0, 0, 0);
-        }
-  };
-#pragma unroll
-  for (int u = 0; u < NS; ++u) { load_a(min(u, nch - 1), fa[u]); load_b(min(u, nch - 1), gb[u]); }
-  stage_b(gb[0], 0);
-  load_b(min(NS, nch - 1), gb[0]);
-  __syncthreads();
-  for (int c = 0; c < nch; c += NS) {
-#pragma unroll
-    for (int u = 0; u < NS; ++u) {
-      // step c + u: its B image is in buffer u & 1 (NS is even), its A fragments in fa[u]
-      stage_b(gb[(u + 1) % NS], (u + 1) & 1);          // the next step's image (read last in the step before this one)
-      load_b(min(c + u + 1 + NS, nch - 1), gb[(u + 1) % NS]);
-      mma(fa[u], u & 1);
-      load_a(min(c + u + NS, nch - 1), fa[u]);
-      __syncthreads();
-    }
-  }
-}
-
-// X = T L_jj^-T for this wave's 16 x 64 slice T (in acc), by the 16-column substitution of diag_step64_kernel
-// (factor image Sp with perm16 columns, the inverses linv of its 16 x 16 diagonal blocks); X goes to the wave's
-// rows Rw of the LDS row buffer and from there to G (row stride ld), a 512-byte row segment per store.
-// SC1: the rows go out with write-through stores (another workgroup reads them: lml_team_kernel).
-template <bool SC1 = false>
-__device__ __forceinline__ void lmlwg_solve_store(const double4_t (&acc)[4], const double* Sp, const double* linv,
-                                                  double* Rw, double* Tt, double* __restrict__ G, long ld, int lane) {
-  const int kq = lane >> 4, l15 = lane & 15;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    double4_t a1 = acc[b], a2 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int bp = 0; bp < b; ++bp)
-#pragma unroll
-      for (int st = 0; st < 4; ++st) {
-        const double av = Rw[l15 * PBP + 16 * bp + 4 * st + kq];                               // X_b'[i][k]
-        const double bv = -Sp[(16 * b + l15) * SPP_STAGE + perm16(16 * bp + 4 * st + kq)];     // -L[16b+j][16b'+k]
-        if (st & 1) a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, a2, 0, 0, 0);
-        else a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, a1, 0, 0, 0);
-      }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Tt[(kq + 4 * r) * 17 + l15] = a1[r] + a2[r];
-    COMPILER_BARRIER();                              // same wave: LDS executes its operations in order
-    double4_t x = {0.0, 0.0, 0.0, 0.0}, x2 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int st = 0; st < 4; ++st) {
-      const double av = Tt[l15 * 17 + 4 * st + kq];                                            // T[i][k]
-      const double bv = linv[b * (16 * 17) + l15 * 17 + 4 * st + kq];                          // Linv_bb[j][k]
-      if (st & 1) x2 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, x2, 0, 0, 0);
-      else x = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, x, 0, 0, 0);
-    }
-    COMPILER_BARRIER();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Rw[(kq + 4 * r) * PBP + 16 * b + l15] = x[r] + x2[r];
-    COMPILER_BARRIER();
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    if (SC1) __hip_atomic_store(G + (long)i * ld + lane, Rw[i * PBP + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else G[(long)i * ld + lane] = Rw[i * PBP + lane];
-  }
-  COMPILER_BARRIER();                                // (the next tile's substitution overwrites Rw)
-}
-
-// The last diagonal tile of lml_wg_body, staged in Sp by the caller (ring flags zeroed, barrier passed): columns 0 .. klast
-// only, no inverses; leaves the factor image in Sp (perm16 columns).  Returns this wave's first bad column or -1.
-// NOT inlined, for lmlt_factor_tile's reason: next to factor64_waves in one body the register allocator put sixteen
-// registers of the pivot chain into scratch.  LDS pointers formed here, from the dynamic LDS base (lml_wg_body's layout).
-__device__ __attribute__((noinline)) int lmlwg_factor_last(int klast, int* ring_timeout) {
-  extern __shared__ __attribute__((aligned(16))) double dsm[];
-  double* Sp = dsm;
-  double* ring = dsm + PB * SPP_STAGE + PB * PBP + PB;
-  double* tbuf0 = ring + PB * PB;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  double av[16];
-  int bad = tiny64_factor(av, lane, w, Sp, tbuf0 + (w > 0 ? (w - 1) : 0) * PB * 17, ring, klast, ring_timeout);
-  bad = (bad > klast) ? -1 : bad;
-  const bool active = 16 * w <= klast;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) Sp[lane * SPP_STAGE + perm16(16 * w + q)] = active ? av[q] : 0.0;   // (columns nobody reads: defined values all the same)
-  return bad;
-}
-
-// FUSED (round 6): the workgroup first builds its candidate's Gram matrix itself -- descriptor, inputs and labels as
-// k_lml_tiny takes them (kernmat.hip; LmlFuse), scaled inputs in the LDS the factorisation uses later -- writes the n x n
-// lower triangle to Km, and publishes {sum log L_ii, z.z, failed pivot or 0, done} per candidate the way tiny_publish does:
-// a small group of mid-sized candidates (a slice sampler's call at 64 <= n <= 128) is then ONE launch with no copy at all.
-struct LmlFuse {
-  ExpConsts ec;
-  const double* X; long ldx;       // [n x d] raw inputs (device)
-  const char* blob;                // TinyCand[count] | kernel images | y[n]   (pinned host memory when direct)
-  long y_off;
-  double* ybuf;                    // [n] device copy of y (every workgroup writes the same values)
-  double* out4;                    // [count][4]
-  int direct;
-};
-constexpr int LMLF_LDS_DOUBLES = PB * PB + 3 * PB * 17 + 8 * 16 * 17;     // ring .. linv: free until the first factorisation
-
-template <bool FUSED>
-__device__ __forceinline__ void lml_wg_body(const LmlWgArgs& a, const LmlFuse& f) {
-  extern __shared__ __attribute__((aligned(16))) double dsm[];
-  double* Sp = dsm;                                  // [64][SPP] staged diagonal tile, then the factor image (perm16 columns)
-  double* R = dsm + PB * SPP_STAGE;                  // [64][65] solved rows, 16 per wave
-  double* colbuf = R + PB * PBP;                     // [64] reciprocal diagonal
-  double* ring = colbuf + PB;                        // [64][64] published columns of factor64_waves
-  double* tbuf0 = ring + PB * PB;                    // 3 x [64][17] layout buffers, then 4 x [16][17] substitution tiles
-  double* lbb = tbuf0 + 3 * PB * 17;                 // 4 x [16][17]
-  double* linv = lbb + 4 * 16 * 17;                  // 4 x [16][17] inverses of the factor's 16 x 16 diagonal blocks
-  double* rdiag = colbuf;
-  __shared__ int s_badv[4];
-  __shared__ int s_ring_timeout;
-  __shared__ double s_red[8];
-  const int c = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int kq = lane >> 4, l15 = lane & 15;
-  double* __restrict__ Km = a.K + (long)c * a.sK;
-  const long ld = a.ld;
-  const int n = a.n, nbt = a.nbt;
-  double cdiag, mean;
-  if constexpr (FUSED) {
-    __shared__ PartDev parts[TINY_MAX_PARTS];
-    __shared__ double s_fz[4];
-    const TinyCand cand = reinterpret_cast<const TinyCand*>(f.blob)[c];
-    const char* image = f.blob + cand.image;
-    const int P = cand.P, n_parts = cand.n_parts;
-    const size_t off_bw = (sizeof(PartDev) * n_parts + 15) & ~size_t(15);
-    const size_t off_cols = off_bw + ((sizeof(double) * (P ? P : 1) + 15) & ~size_t(15));
-    for (int q = tid; q < n_parts * (int)(sizeof(PartDev) / sizeof(int)); q += 256)
-      reinterpret_cast<int*>(parts)[q] = reinterpret_cast<const int*>(image)[q];
-    const double* bw = reinterpret_cast<const double*>(image + off_bw);
-    const int* cols = reinterpret_cast<const int*>(image + off_cols);
-    const double* yb = reinterpret_cast<const double*>(f.blob + f.y_off);
-    double* Xp = ring;                               // [n][P], then Np [n][n_parts]
-    double* Np = Xp + n * P;
-    double r2 = 0.0;
-    for (int j = tid; j < n; j += 256) { const double v = yb[j]; f.ybuf[j] = v; r2 = fma(v - cand.mean, v - cand.mean, r2); }
-    for (int idx = tid; idx < n * P; idx += 256) {
-      const int row = idx / P, pc = idx - row * P;
-      const int col = cols[pc];
-      Xp[idx] = col >= 0 ? f.X[(long)row * f.ldx + col] / bw[pc] : 0.0;       // kernel.py:179-181
-    }
-    for (int off = 32; off > 0; off >>= 1) r2 += __shfl_down(r2, off, 64);
-    if (lane == 0) s_fz[w] = r2;
-    __syncthreads();
-    for (int idx = tid; idx < n * n_parts; idx += 256) {
-      const int row = idx / n_parts, part = idx - row * n_parts;
-      const PartDev& pd = parts[part];
-      int nreal = 0;
-      for (int q = 0; q < pd.kc; ++q) nreal += cols[pd.poff + q] >= 0;
-      Np[idx] = np_sumsq(Xp + row * P + pd.poff, nreal);                     // general_utils.py:66-67
-    }
-    __syncthreads();
-    // the augmented row's diagonal entry c = 1 + |y - m|^2 / s2 > z.z (a hair of slack for the sum's rounding)
-    mean = cand.mean;
-    const double rr = ((s_fz[0] + s_fz[1]) + (s_fz[2] + s_fz[3])) * (1.0 + 1e-6);
-    cdiag = 1.0 + rr / cand.noise;
-    if (!(cand.noise > 0.0) || !(cdiag < INFINITY)) {          // (uniform) nothing bounds z.z: the host takes this candidate elsewhere
-      if (tid == 0) tiny_publish(f.out4 + 4 * (long)c, f.direct != 0, NAN, NAN, -1.0, 1.0);
-      return;
-    }
-    // K + noise I, lower triangle (gp_core.py:843)
-    tiny_gram_lower(cand, parts, n_parts, Xp, P, Np, n, f.ec,
-                    [&](int i, int j, double v) { Km[(long)i * ld + j] = (i == j) ? v + cand.noise : v; });
-    // the matrix and the labels are out: every wave drains its stores, then all of them may read
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  } else {
-    cdiag = a.par[c];
-    mean = a.par[a.count + c];
-  }
-  double* Rw = R + 16 * w * PBP;
-  double* Tt = tbuf0 + w * (16 * 17);
-  for (int j = 0; j < nbt; ++j) {
-    double4_t acc[2][4];
-    // (round 6) the LAST diagonal tile is read only as far as the last observation's column: sum log L_ii runs over the
-    // rows of K, and row n of the factor -- z -- is final in column k as soon as column k is.  Its factorisation stops
-    // there, and when the tile holds the augmented row alone (n a multiple of 64) the whole block column is not needed.
-    const int klast = (j == nbt - 1) ? n - 1 - 64 * j : 63;
-    if (klast < 0) break;
-    // ---- tile rows j (the diagonal tile) and j + 1 ----
-    const bool two = j + 1 < nbt;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[1][t] = (double4_t){0.0, 0.0, 0.0, 0.0};
-    lmlwg_load_tile(a, Km, mean, cdiag, j, j, w, kq, l15, acc[0]);
-    if (two) lmlwg_load_tile(a, Km, mean, cdiag, j + 1, j, w, kq, l15, acc[1]);
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[q][t] = -acc[q][t];       // the products ADD: -T = -A + sum L L^T
-    if (two) lmlwg_gemm<2>(Km, ld, j, j, w, kq, l15, acc, ring);
-    else lmlwg_gemm<1>(Km, ld, j, j, w, kq, l15, acc, ring);
-    // the diagonal tile -> staged block (lower triangle, zero above)
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * w + kq + 4 * r, col = 16 * t + l15;
-        Sp[row * SPP_STAGE + col] = (col <= row) ? -acc[0][t][r] : 0.0;
-      }
-    if (tid < PB) ring[tid * PB] = 0.0;                // row-0 entries double as the "published" flags
-    if (tid == 0) s_ring_timeout = 0;
-    __syncthreads();
-    {
-      double av[16];
-      double* tbuf = tbuf0 + (w > 0 ? (w - 1) : 0) * PB * 17;
-      if (klast < 63) {
-        const int bad = lmlwg_factor_last(klast, &s_ring_timeout);
-        if (lane == 0) s_badv[w] = bad;
-      } else {
-        const int bad = factor64_waves<false>(av, lane, w, Sp, tbuf, ring, lbb, linv, rdiag, &s_ring_timeout);
-        if (lane == 0) s_badv[w] = bad;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) Sp[lane * SPP_STAGE + perm16(16 * w + q)] = av[q];
-      }
-    }
-    __syncthreads();
-    const int s_bad = (s_badv[0] >= 0) ? s_badv[0] : (s_badv[1] >= 0) ? s_badv[1] : (s_badv[2] >= 0) ? s_badv[2] : s_badv[3];
-    if (s_bad >= 0 || s_ring_timeout) {                // (uniform) not positive definite as it stands: the host takes the ladder
-      if (tid == 0) {
-        if constexpr (FUSED) tiny_publish(f.out4 + 4 * (long)c, f.direct != 0, NAN, NAN, (double)(64ll * j + (s_bad >= 0 ? s_bad : 0) + 1), 1.0);
-        else a.info[c] = 64ll * j + (s_bad >= 0 ? s_bad : 0) + 1;
-      }
-      return;
-    }
-    {
-      // L_jj to its place (the likelihood reads its diagonal; later block columns never read a diagonal tile)
-      const int pk = perm16(lane);
-      double* Ljj = Km + (long)(64 * j) * ld + 64 * j;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) Ljj[(long)(w + 4 * r) * ld + lane] = Sp[(w + 4 * r) * SPP_STAGE + pk];
-    }
-    if (two) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[1][t] = -acc[1][t];
-      lmlwg_solve_store(acc[1], Sp, linv, Rw, Tt, Km + (long)(64 * (j + 1) + 16 * w) * ld + 64 * j, ld, lane);
-    }
-    // ---- the tile rows below, two at a time ----
-    for (int i0 = j + 2; i0 < nbt; i0 += 2) {
-      const bool two2 = i0 + 1 < nbt;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[1][t] = (double4_t){0.0, 0.0, 0.0, 0.0};
-      lmlwg_load_tile(a, Km, mean, cdiag, i0, j, w, kq, l15, acc[0]);
-      if (two2) lmlwg_load_tile(a, Km, mean, cdiag, i0 + 1, j, w, kq, l15, acc[1]);
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[q][t] = -acc[q][t];
-      if (two2) lmlwg_gemm<2>(Km, ld, j, i0, w, kq, l15, acc, ring);
-      else lmlwg_gemm<1>(Km, ld, j, i0, w, kq, l15, acc, ring);
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[q][t] = -acc[q][t];
-      lmlwg_solve_store(acc[0], Sp, linv, Rw, Tt, Km + (long)(64 * i0 + 16 * w) * ld + 64 * j, ld, lane);
-      if (two2) lmlwg_solve_store(acc[1], Sp, linv, Rw, Tt, Km + (long)(64 * (i0 + 1) + 16 * w) * ld + 64 * j, ld, lane);
-    }
-    // block column j is out: every wave drains its stores, then all of them may read it as an operand
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  // sum(log L_ii) over the rows of K, z.z over row n (fixed order: deterministic)
-  double ldv = 0.0, dt = 0.0;
-  for (int i = tid; i < n; i += 256) {
-    ldv += log(Km[(long)i * ld + i]);
-    const double z = Km[(long)n * ld + i];
-    dt = fma(z, z, dt);
-  }
-  for (int off = 32; off > 0; off >>= 1) { ldv += __shfl_down(ldv, off, 64); dt += __shfl_down(dt, off, 64); }
-  if (lane == 0) { s_red[w] = ldv; s_red[4 + w] = dt; }
-  __syncthreads();
-  if (tid == 0) {
-    if constexpr (FUSED) {
-      tiny_publish(f.out4 + 4 * (long)c, f.direct != 0, (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]),
-                   (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]), 0.0, 1.0);
-    } else {
-      a.out2[2 * c] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-      a.out2[2 * c + 1] = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256, 1) void lml_wg_kernel(LmlWgArgs a) { lml_wg_body<false>(a, LmlFuse()); }
-__global__ __launch_bounds__(256, 1) void lml_wgf_kernel(LmlWgArgs a, LmlFuse f) { lml_wg_body<true>(a, f); }
-
-// The same objective with a TEAM of T workgroups per candidate (few candidates: one workgroup each would leave
-// most of the device idle and take 3 ms at n = 1000).  Tile row i belongs to member i mod T; in block column j
-//   every member with rows >= j:  waits for brow[j] (tile row j -- the B operand -- is complete up to column
-//                                 j - 1), accumulates its tiles of the column two at a time;
-//   the owner of row j:           takes the diagonal tile first, factors it, hands L_jj (in its place) and the
-//                                 inverses of its 16 x 16 blocks on under diag[j];
-//   the others:                   wait for diag[j] after their first products, fetch that image, substitute;
-//   the owner of row j + 1:       announces brow[j + 1] as soon as its tile (j + 1, j) is out.
-// Hand-offs as in the one-launch panel: write-through (sc1) stores of whatever another member reads, every
-// wave drains its stores, barrier, relaxed flag; the reader polls, takes ONE agent-scope acquire (its CU's L1)
-// and reads with plain loads -- no line is ever read by a member before its final contents are written, so no
-// stale copy can sit in another XCD's L2.  Every wait is bounded (status word -> the host repeats the group with
-// one workgroup per candidate).  A failed pivot is handed on as diag[j] = 2: every member that still has rows
-// waits for exactly that flag and leaves.  Nothing here assumes where a workgroup runs; co-residency of the
-// T * count <= CUs workgroups is what makes it fast, the bounded waits are what makes it safe.
-__device__ __forceinline__ int lmlt_wait(const int* p, const LmlWgArgs& a, int* s_val) {
-  if (threadIdx.x == 0) {
-    int spins = 0, v;
-    while ((v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-      if (++spins > a.spin_limit) { atomicOr(a.status, (unsigned long long)SYNC_ST_FUSED); v = -1; break; }
-      if ((spins & 63) == 0 && __hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { v = -1; break; }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    *s_val = v;
-  }
-  __syncthreads();
-  const int v = *s_val;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // this CU's L1 holds nothing older than the flag
-  __syncthreads();                                     // (s_val may be rewritten by the next wait)
-  return v;
-}
-__device__ __forceinline__ void lmlt_publish(int* p, int v) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // every wave: its write-through stores are acknowledged
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// LDS images of the one-workgroup objective (dynamic LDS, the layout of diag_step64_kernel, two words behind it)
-struct LmltLds { double *Sp, *R, *ring, *tbuf0, *lbb, *linv, *rdiag; int *badv, *ring_timeout; };
-constexpr int LMLT_SMEM = DIAG_STEP_SMEM + 64;
-__device__ __forceinline__ LmltLds lmlt_lds() {
-  extern __shared__ __attribute__((aligned(16))) double dsm[];
-  LmltLds L;
-  L.Sp = dsm;                                        // [64][SPP] staged diagonal tile, then the factor image (perm16 columns)
-  L.R = dsm + PB * SPP_STAGE;                        // [64][65] solved rows, 16 per wave
-  double* colbuf = L.R + PB * PBP;                   // [64] reciprocal diagonal
-  L.ring = colbuf + PB;                              // [64][64] published columns of factor64_waves
-  L.tbuf0 = L.ring + PB * PB;                        // 3 x [64][17] layout buffers, then 4 x [16][17] substitution tiles
-  L.lbb = L.tbuf0 + 3 * PB * 17;                     // 4 x [16][17]
-  L.linv = L.lbb + 4 * 16 * 17;                      // 4 x [16][17] inverses of the factor's 16 x 16 diagonal blocks
-  L.rdiag = colbuf;
-  L.badv = reinterpret_cast<int*>(dsm + DIAG_STEP_SMEM / 8);
-  L.ring_timeout = L.badv + 4;
-  return L;
-}
-
-// Stage a diagonal tile (this wave's 16 x 64 slice in d0 .. d3), factor it (factor64_waves) and leave the factor image
-// (perm16 columns) in Sp and the inverses of its 16 x 16 blocks in linv.  Returns -1, or the first bad column (64: an
-// LDS ring flag never came up).
-// NOT inlined: inside the team kernel's loop nest the register allocator spilled two dwords of every pivot step of
-// factor64_waves to scratch -- a memory round trip per column on the one chain that is pure latency: 53 us per tile
-// instead of ~10 (tools/dbg_lmlt.py).  As a function of its own the step has the register file to itself; its LDS
-// pointers are formed here, from the dynamic LDS base, so that they stay LDS pointers (passed as arguments they
-// would be generic ones: flat_load instead of ds_read).
-__device__ __attribute__((noinline)) int lmlt_factor_tile(double4_t d0, double4_t d1, double4_t d2, double4_t d3) {
-  const LmltLds L = lmlt_lds();
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int kq = lane >> 4, l15 = lane & 15;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = 16 * w + kq + 4 * r;
-    L.Sp[row * SPP_STAGE + l15] = (l15 <= row) ? d0[r] : 0.0;
-    L.Sp[row * SPP_STAGE + 16 + l15] = (16 + l15 <= row) ? d1[r] : 0.0;
-    L.Sp[row * SPP_STAGE + 32 + l15] = (32 + l15 <= row) ? d2[r] : 0.0;
-    L.Sp[row * SPP_STAGE + 48 + l15] = (48 + l15 <= row) ? d3[r] : 0.0;
-  }
-  if (tid < PB) L.ring[tid * PB] = 0.0;                // row-0 entries double as the "published" flags
-  if (tid == 0) *L.ring_timeout = 0;
-  __syncthreads();
-  {
-    double av[16];
-    double* tbuf = L.tbuf0 + (w > 0 ? (w - 1) : 0) * PB * 17;
-    const int bad = factor64_waves<false>(av, lane, w, L.Sp, tbuf, L.ring, L.lbb, L.linv, L.rdiag, L.ring_timeout);
-    if (lane == 0) L.badv[w] = bad;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) L.Sp[lane * SPP_STAGE + perm16(16 * w + q)] = av[q];
-  }
-  __syncthreads();
-  const int s_bad = (L.badv[0] >= 0) ? L.badv[0] : (L.badv[1] >= 0) ? L.badv[1] : (L.badv[2] >= 0) ? L.badv[2] : L.badv[3];
-  return *L.ring_timeout ? 64 : s_bad;
-}
-
-// ... and hand it on: factor image and inverses to global memory with write-through stores, *flag = 1 -- or 2 after a
-// failed pivot (then info is set and the caller leaves).  Returns false on failure.
-__device__ __forceinline__ bool lmlt_factor_publish(const LmlWgArgs& a, const LmltLds& L, const double4_t (&dacc)[4],
-                                                    double* __restrict__ Km, long ld, int jj, int c, double* linvg,
-                                                    int* flag) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  LSTAMP(a, jj, 10);
-  const int s_bad = lmlt_factor_tile(dacc[0], dacc[1], dacc[2], dacc[3]);
-  LSTAMP(a, jj, 13);
-  if (s_bad >= 0) {
-    if (tid == 0) a.info[c] = 64ll * jj + (s_bad & 63) + 1;
-    lmlt_publish(flag, 2);                             // nobody may hang: the waiters leave on 2
-    return false;
-  }
-  const int pk = perm16(lane);
-  double* Ljj = Km + (long)(64 * jj) * ld + 64 * jj;
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-    __hip_atomic_store(Ljj + (long)(w + 4 * r) * ld + lane, L.Sp[(w + 4 * r) * SPP_STAGE + pk], __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  for (int i = tid; i < LMLT_LINV; i += 256)
-    __hip_atomic_store(linvg + (long)jj * LMLT_LINV + i, L.linv[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  LSTAMP(a, jj, 14);
-  lmlt_publish(flag, 1);
-  LSTAMP(a, jj, 15);
-  return true;
-}
-
-// factor image of block column jj (announced and waited for before) from global memory into Sp / linv
-__device__ __forceinline__ void lmlt_fetch_image(const LmltLds& L, const double* __restrict__ Km, long ld, int jj,
-                                                 const double* linvg) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const double* Ljj = Km + (long)(64 * jj) * ld + 64 * jj;
-  const int pk = perm16(lane);
-  double pre[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) pre[r] = Ljj[(long)(w + 4 * r) * ld + lane];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) L.Sp[(w + 4 * r) * SPP_STAGE + pk] = pre[r];
-  for (int i = tid; i < LMLT_LINV; i += 256) L.linv[i] = linvg[(long)jj * LMLT_LINV + i];
-  __syncthreads();
-}
-
-// Look-ahead (the member that owns tile row j + 1, while block column j is being finished): the NEXT diagonal tile
-// is accumulated over the columns before j while the member waits for L_jj anyway, takes the product with the
-// just-solved tile (j + 1, j) straight from the LDS row buffer, and is factored and announced before the member
-// turns to the rest of its rows of column j -- so that a block column's critical path is
-//     L_jj announced -> fetch -> substitution of ONE tile -> K = 64 product -> 64 x 64 factorisation -> announce
-// whatever j (the left-looking products over 64 j columns had been on it: 1.7 j us per column).
-__global__ __launch_bounds__(256, 1) void lml_team_kernel(LmlWgArgs a) {
-  const LmltLds L = lmlt_lds();
-  __shared__ int s_wait;
-  __shared__ double s_red[8];
-  const int T = a.T;
-  const int c = blockIdx.x / T, t = blockIdx.x - c * T;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int kq = lane >> 4, l15 = lane & 15;
-  double* __restrict__ Km = a.K + (long)c * a.sK;
-  const long ld = a.ld;
-  const int n = a.n, nbt = a.nbt;
-  const double cdiag = a.par[c], mean = a.par[a.count + c];
-  int* dflag = a.sync + (long)c * LMLT_SYNC_INTS;
-  int* bflag = dflag + 32;
-  double* linvg = a.linvbuf + (long)c * nbt * LMLT_LINV;
-  double* Rw = L.R + 16 * w * PBP;
-  double* Tt = L.tbuf0 + w * (16 * 17);
-  int lds_image = -1;                                  // block column whose factor image Sp / linv hold
-  int factored = -1;                                   // last diagonal tile this member has factored and announced
-  double4_t dacc[2][4];                                // [0]: the look-ahead diagonal tile ([1] unused: lmlwg_gemm's signature)
-  for (int j = 0; j < nbt; ++j) {
-    const int own_j = j % T;
-    const bool owner = own_j == t;
-    const bool next_owner = (j + 1 < nbt) && ((j + 1) % T == t);
-    const int i_first = j + ((t - own_j + T) % T);     // this member's first tile row >= j
-    if (i_first >= nbt) break;                         // no rows left in this or any later column
-    LSTAMP(a, j, 0);
-    if (next_owner) {
-      // look-ahead, part 1: the next diagonal tile over the columns before j (tile row j + 1 on both sides: this member's
-      // own tiles) -- BEFORE the wait for tile row j, whose owner is busy with this column's diagonal tile right now
-      lmlwg_load_tile(a, Km, mean, cdiag, j + 1, j + 1, w, kq, l15, dacc[0]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) dacc[0][q] = -dacc[0][q];
-      lmlwg_gemm<1>(Km, ld, j, j + 1, w, kq, l15, dacc, L.ring, T, j + 1);
-      LSTAMP(a, j, 3);
-    }
-    if (j > 0 && !owner) {
-      // tile row j (the B operand of this column) was completed by its owner in column j - 1
-      if (lmlt_wait(bflag + j, a, &s_wait) != 1) return;
-    }
-    LSTAMP(a, j, 1);
-    if (owner && factored < j) {
-      // (j = 0, or a team of one: no look-ahead has prepared this tile)
-      lmlwg_load_tile(a, Km, mean, cdiag, j, j, w, kq, l15, dacc[0]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) dacc[0][q] = -dacc[0][q];
-      lmlwg_gemm<1>(Km, ld, j, j, w, kq, l15, dacc, L.ring, T);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) dacc[0][q] = -dacc[0][q];
-      __syncthreads();
-      if (!lmlt_factor_publish(a, L, dacc[0], Km, ld, j, c, linvg, dflag + j)) return;
-      factored = j; lds_image = j;
-    }
-    bool waited = owner;                               // diag[j] seen (the owner wrote it)
-    for (int i0 = owner ? j + T : i_first, inext; i0 < nbt; i0 = inext) {
-      const int i1 = i0 + T;
-      const bool two = i1 < nbt;
-      inext = i1 + T;
-      const bool la = next_owner && i0 == j + 1;       // this group starts with tile (j + 1, j)
-      double4_t acc[2][4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[1][q] = (double4_t){0.0, 0.0, 0.0, 0.0};
-      lmlwg_load_tile(a, Km, mean, cdiag, i0, j, w, kq, l15, acc[0]);
-      if (two) lmlwg_load_tile(a, Km, mean, cdiag, i1, j, w, kq, l15, acc[1]);
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int q2 = 0; q2 < 4; ++q2) acc[q][q2] = -acc[q][q2];
-      if (two) lmlwg_gemm<2>(Km, ld, j, i0, w, kq, l15, acc, L.ring, T);
-      else lmlwg_gemm<1>(Km, ld, j, i0, w, kq, l15, acc, L.ring, T);
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int q2 = 0; q2 < 4; ++q2) acc[q][q2] = -acc[q][q2];
-      if (i0 == (owner ? j + T : i_first)) LSTAMP(a, j, 2);
-      if (!waited) {
-        const int v = lmlt_wait(dflag + j, a, &s_wait);
-        if (v != 1) return;                            // 2: not positive definite (reported by the owner); -1: gave up
-        waited = true;
-        LSTAMP(a, j, 4);
-      }
-      if (lds_image != j) { lmlt_fetch_image(L, Km, ld, j, linvg); lds_image = j; }
-      if (i0 == (owner ? j + T : i_first)) LSTAMP(a, j, 5);
-      lmlwg_solve_store<true>(acc[0], L.Sp, L.linv, Rw, Tt, Km + (long)(64 * i0 + 16 * w) * ld + 64 * j, ld, lane);
-      if (i0 == (owner ? j + T : i_first)) LSTAMP(a, j, 6);
-      if (la) {
-        // -dacc += X X^T, X = tile (j + 1, j): this wave's rows and all 64 rows from the LDS row buffer
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-          const double av = Rw[l15 * PBP + 4 * ks + kq];
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            dacc[0][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, L.R[(16 * q + l15) * PBP + 4 * ks + kq], dacc[0][q], 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dacc[0][q] = -dacc[0][q];
-        // tile row j + 1 is complete up to column j: the next column's B operand (the barrier inside also frees the row buffer)
-        lmlt_publish(bflag + j + 1, 1);
-        LSTAMP(a, j, 7);
-      }
-      if (two) lmlwg_solve_store<true>(acc[1], L.Sp, L.linv, Rw, Tt, Km + (long)(64 * i1 + 16 * w) * ld + 64 * j, ld, lane);
-      if (la) {
-        // the next diagonal tile now, ahead of this member's other rows of column j
-        __syncthreads();                               // every wave is done with the image of column j
-        if (!lmlt_factor_publish(a, L, dacc[0], Km, ld, j + 1, c, linvg, dflag + j + 1)) return;
-        factored = j + 1; lds_image = j + 1;
-        LSTAMP(a, j, 8);
-      }
-    }
-    // this member's tiles of column j are out: its own waves may read them as operands
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    LSTAMP(a, j, 9);
-  }
-  // the owner of the last tile row holds row n (z) and has waited for every diagonal tile
-  if (t != (nbt - 1) % T) return;
-  double ldv = 0.0, dt = 0.0;
-  for (int i = tid; i < n; i += 256) {
-    ldv += log(Km[(long)i * ld + i]);
-    const double z = Km[(long)n * ld + i];
-    dt = fma(z, z, dt);
-  }
-  for (int off = 32; off > 0; off >>= 1) { ldv += __shfl_down(ldv, off, 64); dt += __shfl_down(dt, off, 64); }
-  if (lane == 0) { s_red[w] = ldv; s_red[4 + w] = dt; }
-  __syncthreads();
-  if (tid == 0) {
-    a.out2[2 * c] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-    a.out2[2 * c + 1] = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
-  }
-}
+namespace {
 
 // ---------------------------------------------------------------------------------------------
 // Panel strips.  Once the 512 x 512 diagonal block of a panel is factored, the rows below it are
@@ -1720,8 +1015,30 @@ int block_inverse_quality(dfh_ctx* ctx, const double* D, int64_t lda, int64_t nb
   return DFH_OK;
 }
 
+// The factorisation's run-time switches, read once per process at the first factorisation.
+// chol_plan, below, turns them into one call's choices.
+struct CholSwitches {
+  // test hook: DFH_TEST_SPIN_LIMIT=0 makes every inter-workgroup wait expire at once (the fallback's test)
+  int spin_limit = env_int("DFH_TEST_SPIN_LIMIT", SPIN_LIMIT_DEFAULT);
+  int lr_on = env_int("DFH_CHOL_LR", 1);
+  long lr_min_rem = env_int("DFH_CHOL_LR_MIN_REM", 7680);
+  int fused_on = env_int("DFH_CHOL_FUSED", 1);
+  int fused_max_batch = env_int("DFH_CHOL_FUSED_MAX_BATCH", -1);      // < 0: by size (chol_plan)
+  int prog_sleep = env_int("DFH_CHOL_PROG_SLEEP", 8);
+  int strips_on = env_int("DFH_CHOL_STRIPS", 1);
+  int strips_max_wg = env_int("DFH_CHOL_STRIPS_MAX_WG", 1 << 30);
+  int strips_min_wg = env_int("DFH_CHOL_STRIPS_MIN_WG", -1);          // < 0: by batch size (chol_plan)
+  bool pair_on = env_flag("DFH_CHOL_PAIR", true);
+  long pair_min_rem = env_long("DFH_CHOL_PAIR_MIN_REM", 6144L);
+  double refine_tol = env_double("DFH_REFINE_TOL", 1e-13);
+};
+const CholSwitches& chol_switches() {
+  static const CholSwitches sw;
+  return sw;
+}
+
 int refine_steps(double delta) {
-  static const double tol = env_double("DFH_REFINE_TOL", 1e-13);
+  const double tol = chol_switches().refine_tol;
   // test hook (tests/test_gpu_refine_steps.py): every block takes this many steps whatever its inverse is like
   static const int forced = env_int("DFH_REFINE_FORCE_STEPS", -1);
   if (forced >= 0) return forced > 8 ? 8 : forced;
@@ -1769,6 +1086,325 @@ namespace {
 constexpr int LR_REFINE_MAX = 1;   // (each step is two launches on the chain, usually no-ops of ~45 us beside the update)
 const double LR_REFINE_THR[3] = {0.0 /* = the tolerance, filled in at run time */, 3.1622776601683794e-8, 1e-5};
 
+// What one call does with the switches: the only place that knows the thresholds.
+struct CholPlan {
+  int nbatch;
+  int spin_limit;
+  // One launch per panel (panel_fused_kernel) for single matrices / small batches: n = 4096 2.92 -> 2.50 ms,
+  // 8192 8.05 -> 7.07, 16384 34.8 -> 33.4.  Large lock-step batches keep the pivot steps + strips: their
+  // workgroups would spend the diagonal chain's 190 us spinning.
+  // (round 3: lock-step batches of up to 16 gained 5-14 % from it as well, 32 and more lost.  Round 4, with the
+  //  transposed panel -- tools/time_lml_batch.py, tools/r4_run18.sh: 32 matrices gain 4 % (n = 3000) to 20 % (n = 600),
+  //  64 matrices 7-21 % up to n = 1500 and nothing at n = 3000: up to 32 matrices always, up to 64 while n <= 2048)
+  int fused_max_batch;
+  bool fused_mode;
+  // Panel strips (panel_strip_kernel) for lock-step batches: there the pivot steps are throughput-bound
+  // (64 matrices x 64 workgroups, each re-factoring the pivot block, one workgroup per CU) and the
+  // K = 64 panel updates HBM-bound (1.85 GB per step).  A single matrix keeps the pivot-step / GEMM
+  // pairs: its chain is bound by launch latency, which the strips do not shorten (DESIGN.md section 7).
+  // from how many row strips on: 129 in a lock-step batch (round 3, tools/prof_lml.py: 20 - 64 matrices of
+  // n = 600 ... 2000 gain 5 - 20 % over the 513 of round 2; below ~100 strips the pivot steps win), 513 for a
+  // single matrix (which takes the one-launch panel anyway unless that is switched off)
+  int strips_min_wg;
+  // the resident schedule solves the panels with the 512-block inverses: a caller that keeps none gets them from scratch
+  bool borrow_inv;
+  int64_t kb_lr;                              // panels [0, kb_lr) take the resident schedule
+
+  bool strips(int64_t rem, int64_t nbk) const {
+    const CholSwitches& sw = chol_switches();
+    const int64_t wgs = (int64_t)nbatch * ((rem + PB - 1) / PB);
+    return sw.strips_on && rem > 0 && nbk == CHOL_NB && wgs <= sw.strips_max_wg && wgs >= strips_min_wg;
+  }
+  // paired trailing updates while the trailing matrix is large (decided per pair, on the rows left
+  // below its FIRST panel, so that both panels of a pair see the same answer)
+  bool paired(int64_t kb, int64_t rem) const {
+    const CholSwitches& sw = chol_switches();
+    return sw.pair_on && ((kb & 1) ? rem + CHOL_NB : rem) > sw.pair_min_rem;
+  }
+};
+
+CholPlan chol_plan(int64_t n, int nbatch, bool has_keep_inv, bool inv64_only, bool allow_lr, bool safe) {
+  const CholSwitches& sw = chol_switches();
+  const int64_t NB = CHOL_NB;
+  CholPlan p;
+  p.nbatch = nbatch;
+  p.spin_limit = sw.spin_limit;
+  p.fused_max_batch = sw.fused_max_batch >= 0 ? sw.fused_max_batch : (n <= 2048 ? 64 : 32);
+  p.fused_mode = sw.fused_on && nbatch <= p.fused_max_batch && !safe;   // safe: no inter-workgroup hand-offs
+  p.strips_min_wg = sw.strips_min_wg >= 0 ? sw.strips_min_wg : (nbatch > 1 ? 129 : 513);
+  const int64_t lr_floor = sw.lr_min_rem > 640 ? sw.lr_min_rem : 640;     // >= 5 tile rows for the look-ahead order
+  const bool lr_allowed = sw.lr_on && allow_lr && !safe && nbatch == 1 && !inv64_only;
+  p.borrow_inv = !has_keep_inv && lr_allowed && n - NB >= lr_floor;
+  p.kb_lr = 0;
+  if (lr_allowed && (has_keep_inv || p.borrow_inv) && p.fused_mode) {
+    while (n - (p.kb_lr + 1) * NB >= lr_floor) ++p.kb_lr;
+    p.kb_lr &= ~(int64_t)1;                   // the chain schedule pairs panels from an even index on
+  }
+  return p;
+}
+
+// The buffers and strides of one call, and the panel the loop is at.
+struct CholCall {
+  dfh_ctx* ctx;
+  CholPlan plan;
+  double* A; int64_t n, lda, strideA; int nbatch;
+  double* keep_inv; int64_t strideInv; bool inv64_only;
+  int64_t nblk_all, clean_blocks;
+  // Three streams.  P (high priority): the dependent chain -- 64-wide pivot steps over the panel,
+  // each solving ALL rows below it by substitution, then the update of the next block column.
+  // M (the caller's stream): the big trailing updates.  X (aux): everything the chain does not
+  // need -- moving the pivot-block factors into place and the explicit 512-block inverses kept
+  // for the triangular solves of the posterior.
+  hipStream_t M, P, X;
+  long long* d_info; unsigned long long* d_status;
+  double *Lscr_all, *Iscr_all;                // factor scratch [parity][8][64][64] per matrix; the 16 x 16 inverses of those blocks, same parity scheme
+  int* fsync_all;                             // [nbatch][FUSED_SYNC_INTS] counters of the fused panels
+  int64_t strideL, strideT, strideI;
+  double* T;
+  double* d_delta;                            // [nbatch][nblk] quality of the kept block inverses
+  GemmBatch bA;                               // every operand inside the batch matrices
+  int* lr_sync;                               // per panel {diag workgroups resident, next diagonal block's tiles done, next block column's tiles done, -}
+  double *lr_X, *lr_R;                        // the solved rows (two buffers, alternating), their residual (rows below the first panel x 512 each)
+  int64_t lr_xstride;
+  // the panel
+  int64_t kb, k0, nbk, rem;                   // index, first column, width, rows below
+  double *D, *Linv, *Lscr, *Iscr;             // diagonal block, its inverse's slot (or null), this parity's scratch
+};
+
+// The context's event slots of the factorisation (common.h: two per call, then five per panel).
+enum CholEvent { CE_PANEL = 0, CE_TRAIL, CE_AUX, CE_DIAG, CE_COPY };
+int call_event(dfh_ctx* ctx, int which, hipEvent_t* out) { return ctx_event(ctx, EV_CHOL_BASE + (size_t)which, out); }   // 0: start, 1: done
+// (null for a panel before the first: nothing to wait for)
+int panel_event(dfh_ctx* ctx, int64_t kb, CholEvent which, hipEvent_t* out) {
+  *out = nullptr;
+  return kb < 0 ? DFH_OK : ctx_event(ctx, EV_CHOL_BASE + 2 + 5 * (size_t)kb + (size_t)which, out);
+}
+
+FusedArgs fused_args(const CholCall& c) {
+  FusedArgs fa;
+  fa.D = c.D; fa.lda = c.lda; fa.Lfac = c.Lscr; fa.Linv16 = c.Iscr; fa.sync = c.fsync_all; fa.epoch = (int)c.kb + 1;
+  fa.nbk = (int)c.nbk; fa.rows_below = (int)c.rem; fa.info = c.d_info; fa.pivot_base = (long)c.k0;
+  fa.strideD = c.strideA; fa.strideL = c.strideL; fa.strideI = c.strideI;
+  fa.status = c.d_status; fa.spin_limit = c.plan.spin_limit;
+  fa.resident = nullptr; fa.wait_ptr = nullptr; fa.wait_target = 0; fa.prog_sleep = chol_switches().prog_sleep;
+  return fa;
+}
+
+// ---- off the chain: factor blocks into place, 64-block inverses, 512-block inverse, its quality ----
+// (X: the stream it runs on; after: what it waits for, or null)
+int aux_block(const CholCall& c, hipEvent_t after, hipStream_t X) {
+  dfh_ctx* ctx = c.ctx;
+  const int64_t NB = CHOL_NB;
+  hipEvent_t e_aux;
+  DFH_TRY(panel_event(ctx, c.kb, CE_AUX, &e_aux));
+  StreamSwap on_x(ctx, X);
+  if (after) DFH_HIP(hipStreamWaitEvent(X, after, 0));
+  const bool zero_in_trtri = X != ctx->aux && c.nbk == NB;     // resident panels: one launch less on the chain
+  if (c.Linv && !zero_in_trtri) {
+    if (c.nbatch == 1) {
+      DFH_HIP(hipMemsetAsync(c.Linv, 0, (size_t)NB * NB * 8, X));
+    } else {
+      hipLaunchKernelGGL(k_zero_strided, dim3(64, (unsigned)c.nbatch), dim3(256), 0, X, c.Linv, (long)(NB * NB), (long)c.strideInv);
+      DFH_LAUNCH_CHECK();
+    }
+  }
+  hipLaunchKernelGGL(trtri64_kernel, dim3((unsigned)((c.nbk + PB - 1) / PB), (unsigned)c.nbatch), dim3(256), 0, X,
+                     c.D, (long)c.lda, (int)c.nbk, c.Linv, (long)NB, c.Lscr, (long)c.strideA, (long)c.strideInv,
+                     (long)c.strideL, zero_in_trtri ? 1 : 0);
+  DFH_LAUNCH_CHECK();
+  if (c.Linv && !c.inv64_only) {
+    DFH_TRY(assemble_block_inverse(ctx, c.D, c.lda, c.nbk, c.Linv, c.T, c.nbatch, c.strideA, c.strideInv, c.strideT));
+    // clean copy of the block behind the inverses (keep_inv + nblk*NB*NB + ...) and delta = max|I - M L_bb|
+    DFH_TRY(block_inverse_quality(ctx, c.D, c.lda, c.nbk, c.Linv, c.Linv + c.clean_blocks * NB * NB, c.T, c.d_delta + c.kb, c.nbatch,
+                                  c.strideA, c.strideInv, c.strideT, c.nblk_all));
+  }
+  DFH_HIP(hipEventRecord(e_aux, X));
+  return DFH_OK;
+}
+
+// =============== resident look-ahead panel (see the comment above this namespace) ===============
+int panel_resident(const CholCall& c) {
+  dfh_ctx* ctx = c.ctx;
+  const int64_t NB = CHOL_NB, kb = c.kb, k0 = c.k0, rem = c.rem, lda = c.lda;
+  const hipStream_t M = c.M, P = c.P, X = c.X;
+  double* const A = c.A;
+  const int spin_limit = c.plan.spin_limit;
+  hipEvent_t e_panel, e_trail, e_diag, e_copy, e_aux_prev2, e_trail_prev2, e_copy_prev2;
+  DFH_TRY(panel_event(ctx, kb, CE_PANEL, &e_panel));
+  DFH_TRY(panel_event(ctx, kb, CE_TRAIL, &e_trail));
+  DFH_TRY(panel_event(ctx, kb, CE_DIAG, &e_diag));
+  DFH_TRY(panel_event(ctx, kb, CE_COPY, &e_copy));
+  DFH_TRY(panel_event(ctx, kb - 2, CE_AUX, &e_aux_prev2));
+  DFH_TRY(panel_event(ctx, kb - 2, CE_TRAIL, &e_trail_prev2));
+  DFH_TRY(panel_event(ctx, kb - 2, CE_COPY, &e_copy_prev2));
+  int* sy = c.lr_sync + 4 * kb;
+  double* A21 = A + (k0 + NB) * lda + k0;          // rem x 512: the rows below the diagonal block
+  double* Xk = c.lr_X + (kb & 1) * c.lr_xstride;
+  {
+    StreamSwap on_p(ctx, P);
+    if (e_aux_prev2) DFH_HIP(hipStreamWaitEvent(P, e_aux_prev2, 0));     // factor scratch of this parity is free again
+    // Not before update(kb-2) has finished: the eight workgroups need whole CUs, and a high-priority
+    // launch that is PENDING because it does not fit throttles the dispatch of the running update
+    // (measured: update(0) 2.42 ms with this launch enqueued after it, 2.52 / 2.71 ms with it pending
+    // for the last 0.45 / 1.2 ms).  update(kb-1) cannot start before update(kb-2) has ended anyway.
+    if (e_trail_prev2) DFH_HIP(hipStreamWaitEvent(P, e_trail_prev2, 0));
+    FusedArgs fa = fused_args(c);
+    fa.nbk = (int)NB; fa.rows_below = 0;
+    fa.resident = sy;
+    fa.wait_ptr = kb > 0 ? sy - 4 + 1 : nullptr;   // the sixteen... ten lower tiles of this diagonal block, out of update(kb-1)
+    fa.wait_target = 10;
+    hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)(NB / PB), 1), dim3(256), FUSED_SMEM, P, fa);
+    DFH_LAUNCH_CHECK();
+    DFH_HIP(hipEventRecord(e_diag, P));
+  }
+  // the inverse is ON the chain here (the panel solve multiplies by it): it runs on the priority
+  // stream -- on the auxiliary stream its small kernels wait for a slot behind the trailing update's
+  // pending workgroups (trtri64: 36 us alone, 1.3 - 1.8 ms beside the update)
+  DFH_TRY(aux_block(c, nullptr, P));
+  {
+    StreamSwap on_p(ctx, P);
+    if (kb > 0) {
+      // the whole block column has to be out of update(kb-1): 4 T - 6 look-ahead tiles over T tile rows
+      const int64_t Tprev = (rem + NB + 127) / 128;
+      hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, P, (const int*)(sy - 4 + 2), (int)(4 * Tprev - 6), c.d_status, spin_limit);
+      DFH_LAUNCH_CHECK();
+    }
+    const double* Mi = c.Linv;                               // inverse of the diagonal block (lower, ld NB)
+    const double* Lbb = c.Linv + c.clean_blocks * NB * NB;   // its clean copy
+    // the solved rows go to a panel buffer of their own (two, alternating): the trailing update reads
+    // them from there (contiguous, ld 512) and the copy into the factor happens off the chain
+    if (e_copy_prev2) DFH_HIP(hipStreamWaitEvent(P, e_copy_prev2, 0));      // the buffer's previous contents are in place
+    DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, rem, NB, NB, 1.0, A21, lda, Mi, NB, 0.0, nullptr, 0, Xk, NB));
+    for (int st = 0; st < LR_REFINE_MAX; ++st) {
+      // X <- X + (A21 - X L_bb^T) M^T, the right-hand side untouched; skipped on the device unless due
+      ctx->gemm_cond = c.d_delta + kb;
+      ctx->gemm_cond_thr = st == 0 ? chol_switches().refine_tol : LR_REFINE_THR[st];
+      int rc_r = gemm_f64(ctx, GEMM_KTRI_B, rem, NB, NB, -1.0, Xk, NB, Lbb, NB, 1.0, A21, lda, c.lr_R, NB);
+      if (rc_r == DFH_OK) rc_r = gemm_f64(ctx, GEMM_KTRI_B, rem, NB, NB, 1.0, c.lr_R, NB, Mi, NB, 1.0, Xk, NB, Xk, NB);
+      ctx->gemm_cond = nullptr;
+      DFH_TRY(rc_r);
+    }
+    DFH_HIP(hipEventRecord(e_panel, P));
+  }
+  {
+    StreamSwap on_x(ctx, X);
+    DFH_HIP(hipStreamWaitEvent(X, e_panel, 0));
+    DFH_TRY(copy_matrix(ctx, Xk, NB, A21, lda, rem, NB));
+    DFH_HIP(hipEventRecord(e_copy, X));
+  }
+  // ---- M: the whole trailing update with this panel, next block column first ----
+  DFH_HIP(hipStreamWaitEvent(M, e_panel, 0));
+  const bool next_resident = kb + 1 < c.plan.kb_lr;
+  if (next_resident) {
+    hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, M, (const int*)(sy + 4), (int)(NB / PB), c.d_status, spin_limit);
+    DFH_LAUNCH_CHECK();
+  }
+  {
+    double* C = A + (k0 + NB) * lda + (k0 + NB);
+    ctx->gemm_la_cnt = next_resident ? sy + 1 : nullptr;
+    const int rc_u = gemm_f64(ctx, GEMM_LOWER, rem, rem, NB, -1.0, Xk, NB, Xk, NB, 1.0, C, lda, C, lda);
+    ctx->gemm_la_cnt = nullptr;
+    DFH_TRY(rc_u);
+  }
+  DFH_HIP(hipEventRecord(e_trail, M));
+  return DFH_OK;
+}
+
+// =============== chain panel: the look-ahead schedule of the comment above this namespace ===============
+int panel_chain(const CholCall& c) {
+  dfh_ctx* ctx = c.ctx;
+  const int64_t NB = CHOL_NB, kb = c.kb, k0 = c.k0, nbk = c.nbk, rem = c.rem, lda = c.lda;
+  const hipStream_t M = c.M, P = c.P;
+  double* const A = c.A;
+  const int nbatch = c.nbatch;
+  const bool paired = c.plan.paired(kb, rem), strips = c.plan.strips(rem, nbk);
+  hipEvent_t e_panel, e_trail, e_trail_prev, e_aux_prev2, e_copy_prev, e_copy_prev2;
+  DFH_TRY(panel_event(ctx, kb, CE_PANEL, &e_panel));
+  DFH_TRY(panel_event(ctx, kb, CE_TRAIL, &e_trail));
+  DFH_TRY(panel_event(ctx, kb - 1, CE_TRAIL, &e_trail_prev));
+  DFH_TRY(panel_event(ctx, kb - 2, CE_AUX, &e_aux_prev2));
+  DFH_TRY(panel_event(ctx, kb - 1, CE_COPY, &e_copy_prev));
+  DFH_TRY(panel_event(ctx, kb - 2, CE_COPY, &e_copy_prev2));
+  {
+    StreamSwap on_p(ctx, P);
+    if (e_aux_prev2) DFH_HIP(hipStreamWaitEvent(P, e_aux_prev2, 0));     // factor scratch of this parity is free again
+    // the last resident panel's update covered this block column too: it has to be complete, and
+    // the last two resident panels' solved rows have to be in place
+    if (kb == c.plan.kb_lr && kb > 0 && e_trail_prev) {
+      DFH_HIP(hipStreamWaitEvent(P, e_trail_prev, 0));
+      if (e_copy_prev) DFH_HIP(hipStreamWaitEvent(P, e_copy_prev, 0));
+      if (e_copy_prev2) DFH_HIP(hipStreamWaitEvent(P, e_copy_prev2, 0));
+    }
+    const bool fused = c.plan.fused_mode;           // full panels, and the (last) partial one: identity padding
+    if (fused) {
+      // ---- the whole panel in one launch: diagonal block by eight flag-synchronised strips, rows below alongside ----
+      const FusedArgs fa = fused_args(c);
+      hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)((nbk + PB - 1) / PB + (rem + PB - 1) / PB), (unsigned)nbatch),
+                         dim3(256), FUSED_SMEM, P, fa);
+      DFH_LAUNCH_CHECK();
+    }
+    // ---- 64-wide pivot steps: factor, solve every row below, update the rest of the panel ----
+    for (int64_t j0 = 0; j0 < (fused ? 0 : nbk); j0 += PB) {
+      const int w = (int)((nbk - j0 < PB) ? nbk - j0 : PB);
+      double* Djj = c.D + j0 * lda + j0;
+      const int64_t cols_left = nbk - j0 - w;            // panel columns still to be factored
+      // every row below the pivot block -- or, with strips, only those inside the diagonal block
+      const int64_t rows = cols_left + (strips ? 0 : rem);
+      const unsigned nwg = 1 + (unsigned)((rows + PB - 1) / PB);
+      hipLaunchKernelGGL(diag_step64_kernel, dim3(nwg, (unsigned)nbatch), dim3(256), DIAG_STEP_SMEM, P, Djj,
+                         (long)lda, w, (int)rows, (long)(k0 + j0), c.d_info, c.Lscr + (j0 / PB) * PB * PB,
+                         (long)c.strideA, (long)c.strideL, strips ? c.Iscr + (j0 / PB) * (4 * 16 * 17) : (double*)nullptr,
+                         (long)c.strideI);
+      DFH_LAUNCH_CHECK();
+      if (cols_left > 0) {
+        // A[r, c] -= L[r, j] L[c, j]^T for the rows below and the panel columns to the right
+        // (the part above the diagonal of the block is scratch: only the lower triangle is L)
+        double* Pn = c.D + (j0 + w) * lda + j0;                      // rows x w, already solved
+        double* D22 = c.D + (j0 + w) * lda + (j0 + w);
+        DFH_TRY(gemm_f64(ctx, 0, rows, cols_left, w, -1.0, Pn, lda, Pn, lda, 1.0, D22, lda, D22, lda, &c.bA));
+      }
+    }
+    if (strips && !fused) {
+      // ---- the rows below the diagonal block: L21 = A21 L11^-T, 64 rows per workgroup, one launch ----
+      hipLaunchKernelGGL(panel_strip_kernel, dim3((unsigned)((rem + PB - 1) / PB), (unsigned)nbatch), dim3(256),
+                         STRIP_SMEM, P, c.D, (long)lda, c.Lscr, c.Iscr, A + (k0 + nbk) * lda + k0, (int)rem,
+                         (long)c.strideA, (long)c.strideL, (long)c.strideI);
+      DFH_LAUNCH_CHECK();
+    }
+    DFH_HIP(hipEventRecord(e_panel, P));
+    // ---- the next block column, so that the next panel can start before the trailing update ----
+    if (rem > 0) {
+      // kw = width of the panels whose contribution is still missing to the right of this one:
+      // this panel alone, or -- in paired mode, after the second panel of a pair -- both
+      const int64_t kw = (paired && (kb & 1)) ? nbk + NB : nbk;
+      const double* A21 = A + (k0 + nbk) * lda + (k0 + nbk - kw);    // rem x kw, final
+      if (e_trail_prev) DFH_HIP(hipStreamWaitEvent(P, e_trail_prev, 0));
+      const int64_t nb1 = rem < NB ? rem : NB;
+      double* C1 = A + (k0 + nbk) * lda + (k0 + nbk);   // rows k+1.., block column k+1
+      DFH_TRY(gemm_f64(ctx, 0, rem, nb1, kw, -1.0, A21, lda, A21, lda, 1.0, C1, lda, C1, lda, &c.bA));
+    }
+  }
+  DFH_TRY(aux_block(c, e_panel, c.X));
+  // Paired mode: the trailing update runs after every SECOND panel, 1024 wide (the K = 512 update
+  // reads and writes the C tile once per 512 columns of operand: 54 TF/s at n = 15872 against 63 for
+  // K = 1024, tools/syrk_k.py).  The first panel of a pair only updates the next block column (the
+  // look-ahead product above).  Its pivot chain then has no trailing update to run beside, which
+  // costs most of what the wider update wins: n = 16384 35.2 -> 34.6 ms, n = 4096 2.82 -> 2.90 ms
+  // -- hence only while more than DFH_CHOL_PAIR_MIN_REM rows are left.
+  const bool trail_now = !paired || (kb & 1) || rem <= NB;
+  if (rem > NB && trail_now) {
+    const int64_t rem2 = rem - NB;
+    const int64_t kw = (paired && (kb & 1)) ? nbk + NB : nbk;
+    const double* A31 = A + (k0 + nbk + NB) * lda + (k0 + nbk - kw);   // rows k+2.. of the panel(s)
+    double* A33 = A + (k0 + nbk + NB) * lda + (k0 + nbk + NB);
+    DFH_HIP(hipStreamWaitEvent(M, e_panel, 0));
+    DFH_TRY(gemm_f64(ctx, GEMM_LOWER, rem2, rem2, kw, -1.0, A31, lda, A31, lda, 1.0, A33, lda, A33, lda, &c.bA));
+  }
+  // (with nothing for M to do, the record keeps the event chain well-formed for the next panel's wait)
+  DFH_HIP(hipEventRecord(e_trail, M));
+  return DFH_OK;
+}
+
 }  // namespace
 
 static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda, double* keep_inv,
@@ -1778,67 +1414,36 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
   if (info_pivot) for (int b = 0; b < nbatch; ++b) info_pivot[b] = 0;
   if (n <= 0) return DFH_OK;
   const int64_t NB = CHOL_NB;
-  long long* d_info = reinterpret_cast<long long*>(ctx->d_info);
-  unsigned long long* d_status = reinterpret_cast<unsigned long long*>(d_info + CHOL_MAX_BATCH + 8);
-  // Three streams.  P (high priority): the dependent chain -- 64-wide pivot steps over the panel,
-  // each solving ALL rows below it by substitution, then the update of the next block column.
-  // M (the caller's stream): the big trailing updates.  X (aux): everything the chain does not
-  // need -- moving the pivot-block factors into place and the explicit 512-block inverses kept
-  // for the triangular solves of the posterior.
-  hipStream_t M = ctx->stream, P = ctx->side, X = ctx->aux;
-  DFH_HIP(hipMemsetAsync(d_info, 0, 8 * (size_t)nbatch, M));
-  DFH_HIP(hipMemsetAsync(d_status, 0, 8, M));
-  // test hook: DFH_TEST_SPIN_LIMIT=0 makes every inter-workgroup wait expire at once (the fallback's test)
-  static const int spin_limit = env_int("DFH_TEST_SPIN_LIMIT", SPIN_LIMIT_DEFAULT);
-  static const int lr_on = env_int("DFH_CHOL_LR", 1);
-  static const long lr_min_rem = env_int("DFH_CHOL_LR_MIN_REM", 7680);
-  if (!keep_inv && !inv64_only && lr_on && allow_lr && !safe && nbatch == 1 && n - NB >= (lr_min_rem > 640 ? lr_min_rem : 640)) {
-    // the resident schedule solves the panels with the 512-block inverses: a caller that keeps none gets them from scratch
+  CholCall c;
+  c.ctx = ctx; c.A = A; c.n = n; c.lda = lda; c.strideA = strideA; c.nbatch = nbatch; c.inv64_only = inv64_only;
+  c.d_info = reinterpret_cast<long long*>(ctx->d_info);
+  c.d_status = reinterpret_cast<unsigned long long*>(c.d_info + CHOL_MAX_BATCH + 8);
+  const hipStream_t M = c.M = ctx->stream, P = c.P = ctx->side, X = c.X = ctx->aux;
+  DFH_HIP(hipMemsetAsync(c.d_info, 0, 8 * (size_t)nbatch, M));
+  DFH_HIP(hipMemsetAsync(c.d_status, 0, 8, M));
+  const CholPlan plan = c.plan = chol_plan(n, nbatch, keep_inv != nullptr, inv64_only, allow_lr, safe);
+  if (plan.borrow_inv) {
     DFH_TRY(scratch_get(ctx, SCR_CHOLKEEP, (size_t)inv_buffer_doubles(n) * 8, (void**)&keep_inv));
     refine_out = nullptr;
   }
-
-  const int64_t strideInv = keep_inv ? strideKeep : 0;          // between the batch matrices' inverse blocks
-  const int64_t strideL = 2 * (NB / PB) * PB * PB;               // factor scratch: [parity][8][64][64] per matrix
-  const int64_t strideT = NB * NB;
-  const int64_t strideI = 2 * (NB / PB) * (4 * 16 * 17);         // 16 x 16 inverses of those blocks, same parity scheme
-  double* Lscr_all = nullptr;
-  DFH_TRY(scratch_get(ctx, SCR_CHOLINV, ((size_t)nbatch * (strideL + strideI) + (size_t)nbatch * FUSED_SYNC_INTS / 2 + 2) * 8, (void**)&Lscr_all));
-  double* Iscr_all = Lscr_all + (int64_t)nbatch * strideL;
-  int* fsync_all = reinterpret_cast<int*>(Iscr_all + (int64_t)nbatch * strideI);     // [nbatch][FUSED_SYNC_INTS] counters of the fused panels
-  // One launch per panel (panel_fused_kernel) for single matrices / small batches: n = 4096 2.92 -> 2.50 ms,
-  // 8192 8.05 -> 7.07, 16384 34.8 -> 33.4.  Large lock-step batches keep the pivot steps + strips: their
-  // workgroups would spend the diagonal chain's 190 us spinning.
-  static const int fused_on = env_int("DFH_CHOL_FUSED", 1);
-  // (round 3: lock-step batches of up to 16 gained 5-14 % from it as well, 32 and more lost.  Round 4, with the
-  //  transposed panel -- tools/time_lml_batch.py, tools/r4_run18.sh: 32 matrices gain 4 % (n = 3000) to 20 % (n = 600),
-  //  64 matrices 7-21 % up to n = 1500 and nothing at n = 3000: up to 32 matrices always, up to 64 while n <= 2048)
-  static const int fused_max_batch_env = env_int("DFH_CHOL_FUSED_MAX_BATCH", -1);
-  const int fused_max_batch = fused_max_batch_env >= 0 ? fused_max_batch_env : (n <= 2048 ? 64 : 32);
-  const bool fused_mode = fused_on && nbatch <= fused_max_batch && !safe;   // safe: no inter-workgroup hand-offs
-  static const int fused_prog_sleep = env_int("DFH_CHOL_PROG_SLEEP", 8);
-  if (fused_mode) DFH_HIP(hipMemsetAsync(fsync_all, 0, (size_t)nbatch * FUSED_SYNC_INTS * sizeof(int), ctx->stream));
-  // Panel strips (panel_strip_kernel) for lock-step batches: there the pivot steps are throughput-bound
-  // (64 matrices x 64 workgroups, each re-factoring the pivot block, one workgroup per CU) and the
-  // K = 64 panel updates HBM-bound (1.85 GB per step).  A single matrix keeps the pivot-step / GEMM
-  // pairs: its chain is bound by launch latency, which the strips do not shorten (DESIGN.md section 7).
-  static const int strips_on = env_int("DFH_CHOL_STRIPS", 1);
-  static const int strips_max_wg = env_int("DFH_CHOL_STRIPS_MAX_WG", 1 << 30);
-  // from how many row strips on: 129 in a lock-step batch (round 3, tools/prof_lml.py: 20 - 64 matrices of
-  // n = 600 ... 2000 gain 5 - 20 % over the 513 of round 2; below ~100 strips the pivot steps win), 513 for a
-  // single matrix (which takes the one-launch panel anyway unless that is switched off)
-  static const int strips_min_env = env_int("DFH_CHOL_STRIPS_MIN_WG", -1);
-  const int strips_min_wg = strips_min_env >= 0 ? strips_min_env : (nbatch > 1 ? 129 : 513);
-  double* T = nullptr;
-  if (keep_inv) DFH_TRY(scratch_get(ctx, SCR_CHOLT, (size_t)nbatch * strideT * 8, (void**)&T));
-  const int64_t nblk_all = (n + NB - 1) / NB;
+  c.keep_inv = keep_inv;
+  c.strideInv = keep_inv ? strideKeep : 0;          // between the batch matrices' inverse blocks
+  c.strideL = 2 * (NB / PB) * PB * PB;               // factor scratch: [parity][8][64][64] per matrix
+  c.strideT = NB * NB;
+  c.strideI = 2 * (NB / PB) * (4 * 16 * 17);         // 16 x 16 inverses of those blocks, same parity scheme
+  DFH_TRY(scratch_get(ctx, SCR_CHOLINV, ((size_t)nbatch * (c.strideL + c.strideI) + (size_t)nbatch * FUSED_SYNC_INTS / 2 + 2) * 8, (void**)&c.Lscr_all));
+  c.Iscr_all = c.Lscr_all + (int64_t)nbatch * c.strideL;
+  c.fsync_all = reinterpret_cast<int*>(c.Iscr_all + (int64_t)nbatch * c.strideI);
+  if (plan.fused_mode) DFH_HIP(hipMemsetAsync(c.fsync_all, 0, (size_t)nbatch * FUSED_SYNC_INTS * sizeof(int), ctx->stream));
+  c.T = nullptr;
+  if (keep_inv) DFH_TRY(scratch_get(ctx, SCR_CHOLT, (size_t)nbatch * c.strideT * 8, (void**)&c.T));
+  const int64_t nblk = c.nblk_all = (n + NB - 1) / NB;
   // blocks between an inverse and the clean copy of its diagonal block: the block count of the matrix
   // keep_inv was laid out for (this one, unless the call factors a diagonal sub-block of a larger one)
-  if (clean_blocks <= 0) clean_blocks = nblk_all;
-  double* d_delta = nullptr;                  // [nbatch][nblk] quality of the kept block inverses
-  if (keep_inv) DFH_TRY(scratch_get(ctx, SCR_DELTA, (size_t)nbatch * nblk_all * 8, (void**)&d_delta));
-  GemmBatch bA;                               // every operand inside the batch matrices
-  bA.count = nbatch; bA.sA = bA.sB = bA.sCin = bA.sCout = strideA;
+  c.clean_blocks = clean_blocks > 0 ? clean_blocks : nblk;
+  c.d_delta = nullptr;
+  if (keep_inv) DFH_TRY(scratch_get(ctx, SCR_DELTA, (size_t)nbatch * nblk * 8, (void**)&c.d_delta));
+  c.bA.count = nbatch; c.bA.sA = c.bA.sB = c.bA.sCin = c.bA.sCout = strideA;
 
   static bool attr_set_dev[DFH_MAX_DEVICES] = {false};
   bool& attr_set = attr_set_dev[ctx->device];
@@ -1851,268 +1456,49 @@ static int cholesky_device_impl(dfh_ctx* ctx, double* A, int64_t n, int64_t lda,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_SMEM));
     attr_set = true;
   }
-  const int64_t nblk = (n + NB - 1) / NB;
-  static const bool pair_on = env_flag("DFH_CHOL_PAIR", true);
-  static const long pair_min_rem = env_long("DFH_CHOL_PAIR_MIN_REM", 6144L);
 
-  // ---- resident look-ahead: which panels, and what it needs (nothing may allocate inside the loop:
+  // ---- what the resident look-ahead needs (nothing may allocate inside the loop:
   //      hipMalloc can wait for the device, and a gate kernel may be waiting for a launch not yet enqueued) ----
-  int64_t kb_lr = 0;                          // panels [0, kb_lr) take the resident schedule
-  if (lr_on && allow_lr && !safe && nbatch == 1 && keep_inv && !inv64_only && fused_mode) {
-    const int64_t floor_rem = lr_min_rem > 640 ? lr_min_rem : 640;     // >= 5 tile rows for the look-ahead order
-    while (n - (kb_lr + 1) * NB >= floor_rem) ++kb_lr;
-    kb_lr &= ~(int64_t)1;                     // the schedule below pairs panels from an even index on
-  }
-  int* lr_sync = nullptr;                     // per panel {diag workgroups resident, next diagonal block's tiles done, next block column's tiles done, -}
-  double *lr_X = nullptr, *lr_R = nullptr;    // the solved rows (two buffers, alternating), their residual (rows below the first panel x 512 each)
-  const int64_t lr_xstride = (n - NB) * NB;
+  const int64_t kb_lr = plan.kb_lr;
+  c.lr_sync = nullptr; c.lr_X = c.lr_R = nullptr;
+  c.lr_xstride = (n - NB) * NB;
   if (kb_lr > 0) {
-    DFH_TRY(scratch_get(ctx, SCR_CHOLSYNC, (size_t)kb_lr * 4 * sizeof(int), (void**)&lr_sync));
-    DFH_HIP(hipMemsetAsync(lr_sync, 0, (size_t)kb_lr * 4 * sizeof(int), M));
-    DFH_TRY(scratch_get(ctx, SCR_CHOLX, (size_t)2 * lr_xstride * 8, (void**)&lr_X));
-    DFH_TRY(scratch_get(ctx, SCR_CHOLR, (size_t)(n - NB) * NB * 8, (void**)&lr_R));
+    DFH_TRY(scratch_get(ctx, SCR_CHOLSYNC, (size_t)kb_lr * 4 * sizeof(int), (void**)&c.lr_sync));
+    DFH_HIP(hipMemsetAsync(c.lr_sync, 0, (size_t)kb_lr * 4 * sizeof(int), M));
+    DFH_TRY(scratch_get(ctx, SCR_CHOLX, (size_t)2 * c.lr_xstride * 8, (void**)&c.lr_X));
+    DFH_TRY(scratch_get(ctx, SCR_CHOLR, (size_t)(n - NB) * NB * 8, (void**)&c.lr_R));
   }
-  static const double refine_tol = env_double("DFH_REFINE_TOL", 1e-13);
-  hipEvent_t ev_start, ev_done;
-  DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 0, &ev_start));
-  DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 1, &ev_done));
+  hipEvent_t ev_start, ev_done, e_aux_last;
+  DFH_TRY(call_event(ctx, 0, &ev_start));
+  DFH_TRY(call_event(ctx, 1, &ev_done));
   DFH_HIP(hipEventRecord(ev_start, M));
   DFH_HIP(hipStreamWaitEvent(P, ev_start, 0));
   DFH_HIP(hipStreamWaitEvent(X, ev_start, 0));
 
   for (int64_t kb = 0; kb < nblk; ++kb) {
-    const int64_t k0 = kb * NB;
-    const int64_t nbk = (n - k0 < NB) ? n - k0 : NB;
-    double* Linv = keep_inv ? keep_inv + kb * NB * NB : nullptr;
-    double* D = A + k0 * lda + k0;
-    double* Lscr = Lscr_all + (kb & 1) * (NB / PB) * PB * PB;
-    double* Iscr = Iscr_all + (kb & 1) * (NB / PB) * (4 * 16 * 17);
-    const int64_t rem = n - k0 - nbk;
-    // paired trailing updates while the trailing matrix is large (decided per pair, on the rows left
-    // below its FIRST panel, so that both panels of a pair see the same answer)
-    const bool paired = pair_on && ((kb & 1) ? rem + NB : rem) > pair_min_rem;
-    const bool strips = strips_on && rem > 0 && nbk == NB && (int64_t)nbatch * ((rem + PB - 1) / PB) <= strips_max_wg &&
-                        (int64_t)nbatch * ((rem + PB - 1) / PB) >= strips_min_wg;
-    hipEvent_t e_panel, e_trail, e_aux, e_diag, e_trail_prev = nullptr, e_aux_prev2 = nullptr;
-    hipEvent_t e_copy, e_copy_prev = nullptr, e_copy_prev2 = nullptr;
-    DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 2 + 5 * kb, &e_panel));
-    DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 3 + 5 * kb, &e_trail));
-    DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 4 + 5 * kb, &e_aux));
-    DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 5 + 5 * kb, &e_diag));
-    DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 6 + 5 * kb, &e_copy));
-    if (kb >= 1) DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 3 + 5 * (kb - 1), &e_trail_prev));
-    if (kb >= 2) DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 4 + 5 * (kb - 2), &e_aux_prev2));
-    if (kb >= 1) DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 6 + 5 * (kb - 1), &e_copy_prev));
-    if (kb >= 2) DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 6 + 5 * (kb - 2), &e_copy_prev2));
-    // ---- off the chain (stream X): factor blocks into place, 64-block inverses, 512-block inverse, its quality ----
-    auto aux_block = [&](hipEvent_t after, hipStream_t X) -> int {     // (X: the stream it runs on)
-      StreamSwap on_x(ctx, X);
-      if (after) DFH_HIP(hipStreamWaitEvent(X, after, 0));
-      const bool zero_in_trtri = X != ctx->aux && nbk == NB;     // resident panels: one launch less on the chain
-      if (Linv && !zero_in_trtri) {
-        if (nbatch == 1) {
-          DFH_HIP(hipMemsetAsync(Linv, 0, (size_t)NB * NB * 8, X));
-        } else {
-          hipLaunchKernelGGL(k_zero_strided, dim3(64, (unsigned)nbatch), dim3(256), 0, X, Linv, (long)(NB * NB), (long)strideInv);
-          DFH_LAUNCH_CHECK();
-        }
-      }
-      hipLaunchKernelGGL(trtri64_kernel, dim3((unsigned)((nbk + PB - 1) / PB), (unsigned)nbatch), dim3(256), 0, X,
-                         D, (long)lda, (int)nbk, Linv, (long)NB, Lscr, (long)strideA, (long)strideInv,
-                         (long)strideL, zero_in_trtri ? 1 : 0);
-      DFH_LAUNCH_CHECK();
-      if (Linv && !inv64_only) {
-        DFH_TRY(assemble_block_inverse(ctx, D, lda, nbk, Linv, T, nbatch, strideA, strideInv, strideT));
-        // clean copy of the block behind the inverses (keep_inv + nblk*NB*NB + ...) and delta = max|I - M L_bb|
-        DFH_TRY(block_inverse_quality(ctx, D, lda, nbk, Linv, Linv + clean_blocks * NB * NB, T, d_delta + kb, nbatch,
-                                      strideA, strideInv, strideT, nblk_all));
-      }
-      DFH_HIP(hipEventRecord(e_aux, X));
-      return DFH_OK;
-    };
-    if (kb < kb_lr) {
-      // =============== resident look-ahead panel (see the comment above cholesky_device_impl) ===============
-      int* sy = lr_sync + 4 * kb;
-      double* A21 = A + (k0 + NB) * lda + k0;          // rem x 512: the rows below the diagonal block
-      double* Xk = lr_X + (kb & 1) * lr_xstride;
-      {
-        StreamSwap on_p(ctx, P);
-        if (e_aux_prev2) DFH_HIP(hipStreamWaitEvent(P, e_aux_prev2, 0));     // factor scratch of this parity is free again
-        // Not before update(kb-2) has finished: the eight workgroups need whole CUs, and a high-priority
-        // launch that is PENDING because it does not fit throttles the dispatch of the running update
-        // (measured: update(0) 2.42 ms with this launch enqueued after it, 2.52 / 2.71 ms with it pending
-        // for the last 0.45 / 1.2 ms).  update(kb-1) cannot start before update(kb-2) has ended anyway.
-        if (kb >= 2) {
-          hipEvent_t e_trail_prev2;
-          DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 3 + 5 * (kb - 2), &e_trail_prev2));
-          DFH_HIP(hipStreamWaitEvent(P, e_trail_prev2, 0));
-        }
-        FusedArgs fa;
-        fa.D = D; fa.lda = lda; fa.Lfac = Lscr; fa.Linv16 = Iscr; fa.sync = fsync_all; fa.epoch = (int)kb + 1;
-        fa.nbk = (int)NB; fa.rows_below = 0; fa.info = d_info; fa.pivot_base = (long)k0;
-        fa.strideD = strideA; fa.strideL = strideL; fa.strideI = strideI;
-        fa.status = d_status; fa.spin_limit = spin_limit;
-        fa.prog_sleep = fused_prog_sleep;
-        fa.resident = sy;
-        fa.wait_ptr = kb > 0 ? sy - 4 + 1 : nullptr;   // the sixteen... ten lower tiles of this diagonal block, out of update(kb-1)
-        fa.wait_target = 10;
-        hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)(NB / PB), 1), dim3(256), FUSED_SMEM, P, fa);
-        DFH_LAUNCH_CHECK();
-        DFH_HIP(hipEventRecord(e_diag, P));
-      }
-      // the inverse is ON the chain here (the panel solve multiplies by it): it runs on the priority
-      // stream -- on the auxiliary stream its small kernels wait for a slot behind the trailing update's
-      // pending workgroups (trtri64: 36 us alone, 1.3 - 1.8 ms beside the update)
-      DFH_TRY(aux_block(nullptr, P));
-      {
-        StreamSwap on_p(ctx, P);
-        if (kb > 0) {
-          // the whole block column has to be out of update(kb-1): 4 T - 6 look-ahead tiles over T tile rows
-          const int64_t Tprev = (rem + NB + 127) / 128;
-          hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, P, (const int*)(sy - 4 + 2), (int)(4 * Tprev - 6), d_status, spin_limit);
-          DFH_LAUNCH_CHECK();
-        }
-        const double* Mi = Linv;                               // inverse of the diagonal block (lower, ld NB)
-        const double* Lbb = Linv + clean_blocks * NB * NB;      // its clean copy
-        // the solved rows go to a panel buffer of their own (two, alternating): the trailing update reads
-        // them from there (contiguous, ld 512) and the copy into the factor happens off the chain
-        if (e_copy_prev2) DFH_HIP(hipStreamWaitEvent(P, e_copy_prev2, 0));      // the buffer's previous contents are in place
-        DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, rem, NB, NB, 1.0, A21, lda, Mi, NB, 0.0, nullptr, 0, Xk, NB));
-        for (int st = 0; st < LR_REFINE_MAX; ++st) {
-          // X <- X + (A21 - X L_bb^T) M^T, the right-hand side untouched; skipped on the device unless due
-          ctx->gemm_cond = d_delta + kb;
-          ctx->gemm_cond_thr = st == 0 ? refine_tol : LR_REFINE_THR[st];
-          int rc_r = gemm_f64(ctx, GEMM_KTRI_B, rem, NB, NB, -1.0, Xk, NB, Lbb, NB, 1.0, A21, lda, lr_R, NB);
-          if (rc_r == DFH_OK) rc_r = gemm_f64(ctx, GEMM_KTRI_B, rem, NB, NB, 1.0, lr_R, NB, Mi, NB, 1.0, Xk, NB, Xk, NB);
-          ctx->gemm_cond = nullptr;
-          DFH_TRY(rc_r);
-        }
-        DFH_HIP(hipEventRecord(e_panel, P));
-      }
-      {
-        StreamSwap on_x(ctx, X);
-        DFH_HIP(hipStreamWaitEvent(X, e_panel, 0));
-        DFH_TRY(copy_matrix(ctx, Xk, NB, A21, lda, rem, NB));
-        DFH_HIP(hipEventRecord(e_copy, X));
-      }
-      // ---- M: the whole trailing update with this panel, next block column first ----
-      DFH_HIP(hipStreamWaitEvent(M, e_panel, 0));
-      const bool next_resident = kb + 1 < kb_lr;
-      if (next_resident) {
-        hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, M, (const int*)(sy + 4), (int)(NB / PB), d_status, spin_limit);
-        DFH_LAUNCH_CHECK();
-      }
-      {
-        double* C = A + (k0 + NB) * lda + (k0 + NB);
-        ctx->gemm_la_cnt = next_resident ? sy + 1 : nullptr;
-        const int rc_u = gemm_f64(ctx, GEMM_LOWER, rem, rem, NB, -1.0, Xk, NB, Xk, NB, 1.0, C, lda, C, lda);
-        ctx->gemm_la_cnt = nullptr;
-        DFH_TRY(rc_u);
-      }
-      DFH_HIP(hipEventRecord(e_trail, M));
-      continue;
-    }
-    {
-      StreamSwap on_p(ctx, P);
-      if (e_aux_prev2) DFH_HIP(hipStreamWaitEvent(P, e_aux_prev2, 0));     // factor scratch of this parity is free again
-      // the last resident panel's update covered this block column too: it has to be complete, and
-      // the last two resident panels' solved rows have to be in place
-      if (kb == kb_lr && kb > 0 && e_trail_prev) {
-        DFH_HIP(hipStreamWaitEvent(P, e_trail_prev, 0));
-        if (e_copy_prev) DFH_HIP(hipStreamWaitEvent(P, e_copy_prev, 0));
-        if (e_copy_prev2) DFH_HIP(hipStreamWaitEvent(P, e_copy_prev2, 0));
-      }
-      const bool fused = fused_mode;                  // full panels, and the (last) partial one: identity padding
-      if (fused) {
-        // ---- the whole panel in one launch: diagonal block by eight flag-synchronised strips, rows below alongside ----
-        FusedArgs fa;
-        fa.D = D; fa.lda = lda; fa.Lfac = Lscr; fa.Linv16 = Iscr; fa.sync = fsync_all; fa.epoch = (int)kb + 1;
-        fa.nbk = (int)nbk; fa.rows_below = (int)rem; fa.info = d_info; fa.pivot_base = (long)k0;
-        fa.strideD = strideA; fa.strideL = strideL; fa.strideI = strideI;
-        fa.status = d_status; fa.spin_limit = spin_limit;
-        fa.resident = nullptr; fa.wait_ptr = nullptr; fa.wait_target = 0; fa.prog_sleep = fused_prog_sleep;
-        hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)((nbk + PB - 1) / PB + (rem + PB - 1) / PB), (unsigned)nbatch),
-                           dim3(256), FUSED_SMEM, P, fa);
-        DFH_LAUNCH_CHECK();
-      }
-      // ---- 64-wide pivot steps: factor, solve every row below, update the rest of the panel ----
-      for (int64_t j0 = 0; j0 < (fused ? 0 : nbk); j0 += PB) {
-        const int w = (int)((nbk - j0 < PB) ? nbk - j0 : PB);
-        double* Djj = D + j0 * lda + j0;
-        const int64_t cols_left = nbk - j0 - w;            // panel columns still to be factored
-        // every row below the pivot block -- or, with strips, only those inside the diagonal block
-        const int64_t rows = cols_left + (strips ? 0 : rem);
-        const unsigned nwg = 1 + (unsigned)((rows + PB - 1) / PB);
-        hipLaunchKernelGGL(diag_step64_kernel, dim3(nwg, (unsigned)nbatch), dim3(256), DIAG_STEP_SMEM, P, Djj,
-                           (long)lda, w, (int)rows, (long)(k0 + j0), d_info, Lscr + (j0 / PB) * PB * PB,
-                           (long)strideA, (long)strideL, strips ? Iscr + (j0 / PB) * (4 * 16 * 17) : (double*)nullptr,
-                           (long)strideI);
-        DFH_LAUNCH_CHECK();
-        if (cols_left > 0) {
-          // A[r, c] -= L[r, j] L[c, j]^T for the rows below and the panel columns to the right
-          // (the part above the diagonal of the block is scratch: only the lower triangle is L)
-          double* Pn = D + (j0 + w) * lda + j0;                      // rows x w, already solved
-          double* D22 = D + (j0 + w) * lda + (j0 + w);
-          DFH_TRY(gemm_f64(ctx, 0, rows, cols_left, w, -1.0, Pn, lda, Pn, lda, 1.0, D22, lda, D22, lda, &bA));
-        }
-      }
-      if (strips && !fused) {
-        // ---- the rows below the diagonal block: L21 = A21 L11^-T, 64 rows per workgroup, one launch ----
-        hipLaunchKernelGGL(panel_strip_kernel, dim3((unsigned)((rem + PB - 1) / PB), (unsigned)nbatch), dim3(256),
-                           STRIP_SMEM, P, D, (long)lda, Lscr, Iscr, A + (k0 + nbk) * lda + k0, (int)rem,
-                           (long)strideA, (long)strideL, (long)strideI);
-        DFH_LAUNCH_CHECK();
-      }
-      DFH_HIP(hipEventRecord(e_panel, P));
-      // ---- the next block column, so that the next panel can start before the trailing update ----
-      if (rem > 0) {
-        // kw = width of the panels whose contribution is still missing to the right of this one:
-        // this panel alone, or -- in paired mode, after the second panel of a pair -- both
-        const int64_t kw = (paired && (kb & 1)) ? nbk + NB : nbk;
-        const double* A21 = A + (k0 + nbk) * lda + (k0 + nbk - kw);    // rem x kw, final
-        if (e_trail_prev) DFH_HIP(hipStreamWaitEvent(P, e_trail_prev, 0));
-        const int64_t nb1 = rem < NB ? rem : NB;
-        double* C1 = A + (k0 + nbk) * lda + (k0 + nbk);   // rows k+1.., block column k+1
-        DFH_TRY(gemm_f64(ctx, 0, rem, nb1, kw, -1.0, A21, lda, A21, lda, 1.0, C1, lda, C1, lda, &bA));
-      }
-    }
-    DFH_TRY(aux_block(e_panel, X));
-    // Paired mode: the trailing update runs after every SECOND panel, 1024 wide (the K = 512 update
-    // reads and writes the C tile once per 512 columns of operand: 54 TF/s at n = 15872 against 63 for
-    // K = 1024, tools/syrk_k.py).  The first panel of a pair only updates the next block column (the
-    // look-ahead product above).  Its pivot chain then has no trailing update to run beside, which
-    // costs most of what the wider update wins: n = 16384 35.2 -> 34.6 ms, n = 4096 2.82 -> 2.90 ms
-    // -- hence only while more than DFH_CHOL_PAIR_MIN_REM rows are left.
-    const bool trail_now = !paired || (kb & 1) || rem <= NB;
-    if (rem > NB && trail_now) {
-      const int64_t rem2 = rem - NB;
-      const int64_t kw = (paired && (kb & 1)) ? nbk + NB : nbk;
-      const double* A31 = A + (k0 + nbk + NB) * lda + (k0 + nbk - kw);   // rows k+2.. of the panel(s)
-      double* A33 = A + (k0 + nbk + NB) * lda + (k0 + nbk + NB);
-      DFH_HIP(hipStreamWaitEvent(M, e_panel, 0));
-      DFH_TRY(gemm_f64(ctx, GEMM_LOWER, rem2, rem2, kw, -1.0, A31, lda, A31, lda, 1.0, A33, lda, A33, lda, &bA));
-      DFH_HIP(hipEventRecord(e_trail, M));
-    } else {
-      // nothing for M to do: keep the event chain well-formed for the next panel's wait
-      DFH_HIP(hipEventRecord(e_trail, M));
-    }
+    c.kb = kb;
+    c.k0 = kb * NB;
+    c.nbk = (n - c.k0 < NB) ? n - c.k0 : NB;
+    c.rem = n - c.k0 - c.nbk;
+    c.Linv = keep_inv ? keep_inv + kb * NB * NB : nullptr;
+    c.D = A + c.k0 * lda + c.k0;
+    c.Lscr = c.Lscr_all + (kb & 1) * (NB / PB) * PB * PB;
+    c.Iscr = c.Iscr_all + (kb & 1) * (NB / PB) * (4 * 16 * 17);
+    DFH_TRY(kb < kb_lr ? panel_resident(c) : panel_chain(c));
   }
   DFH_HIP(hipEventRecord(ev_done, P));
   DFH_HIP(hipStreamWaitEvent(M, ev_done, 0));
-  {
-    hipEvent_t e_aux_last;
-    DFH_TRY(ctx_event(ctx, EV_CHOL_BASE + 4 + 5 * (nblk - 1), &e_aux_last));
-    DFH_HIP(hipStreamWaitEvent(M, e_aux_last, 0));
-  }
+  DFH_TRY(panel_event(ctx, nblk - 1, CE_AUX, &e_aux_last));
+  DFH_HIP(hipStreamWaitEvent(M, e_aux_last, 0));
 
-  DFH_HIP(hipMemcpyAsync(ctx->h_info, d_info, 8 * (size_t)nbatch, hipMemcpyDeviceToHost, M));
-  DFH_HIP(hipMemcpyAsync(ctx->h_info + CHOL_MAX_BATCH + 8, d_status, 8, hipMemcpyDeviceToHost, M));
+  DFH_HIP(hipMemcpyAsync(ctx->h_info, c.d_info, 8 * (size_t)nbatch, hipMemcpyDeviceToHost, M));
+  DFH_HIP(hipMemcpyAsync(ctx->h_info + CHOL_MAX_BATCH + 8, c.d_status, 8, hipMemcpyDeviceToHost, M));
   std::vector<double> deltas;
   if (keep_inv && refine_out && inv64_only) {
-    for (size_t i = 0; i < (size_t)nbatch * nblk_all; ++i) refine_out[i] = 0;
+    for (size_t i = 0; i < (size_t)nbatch * nblk; ++i) refine_out[i] = 0;
   } else if (keep_inv && (refine_out || kb_lr > 0)) {
-    deltas.resize((size_t)nbatch * nblk_all);
-    DFH_HIP(hipMemcpyAsync(deltas.data(), d_delta, deltas.size() * 8, hipMemcpyDeviceToHost, M));
+    deltas.resize((size_t)nbatch * nblk);
+    DFH_HIP(hipMemcpyAsync(deltas.data(), c.d_delta, deltas.size() * 8, hipMemcpyDeviceToHost, M));
   }
   DFH_HIP(hipStreamSynchronize(M));
   if (refine_out) for (size_t i = 0; i < deltas.size(); ++i) refine_out[i] = refine_steps(deltas[i]);
@@ -2229,350 +1615,6 @@ int stable_cholesky_device(dfh_ctx* ctx, double* dL, int64_t n, double* keep_inv
   return DFH_ERR_JITTER;
 }
 
-// Right-looking block substitution: once x_i is final it is pushed into every remaining row
-// (wide, short GEMVs -> thousands of independent rows per launch instead of one long dependent
-// chain).  The pass is HBM-bound: the lower triangle of L is read once per solve.
-// ---------------------------------------------------------------------------------------------
-// The two substitutions of GP.build_posterior (gp_core.py:161-163) on the 512-block inverses, round 6.
-// A step of either direction is a chain of two dependent launches -- the block's solve by its explicit inverse, then the
-// block's contribution to everything it feeds -- and the old steps spent their time INSIDE their kernels (trace of round
-// 5: one workgroup per row of 4 KB in the forward update, 15 us; a partial + reduce pair of 16 + 6 us per transposed
-// product; a device-to-device copy per step because the block's solve ran in place).  Here: r is updated in place, the
-// solution goes to a vector of its own (no copy), and each kernel is shaped for its operand:
-//   k_trsv_blk_fwd   z_b = M_b r_b             one wave per row of the lower-triangular inverse, columns <= row only
-//   k_trsv_upd_fwd   r_i -= L[i, b] z_b        eight rows per wave, z_b in registers, 32 KB of loads in flight per wave
-//   k_trsv_blk_bwd   a_b = M_b^T r_b           64 columns per workgroup, rows dealt to sixteen waves, one LDS reduce
-//   k_trsv_upd_bwd   r_j -= L[b, j]^T a_b      64 columns per workgroup, a_b in LDS, sixteen row loads in flight per wave
-// Sums run in a fixed order (deterministic); a block that needs refinement steps takes the general route below.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_trsv_blk_fwd(const double* __restrict__ M, int w, const double* __restrict__ r,
-                                                      double* __restrict__ z) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= w) return;
-  const double2_t* a = reinterpret_cast<const double2_t*>(M + (long)row * CHOL_NB);
-  const double2_t* x = reinterpret_cast<const double2_t*>(r);
-  double s0 = 0.0, s1 = 0.0;
-  for (int j = lane; 2 * j <= row; j += 64) {          // (the inverse is exactly zero above its diagonal)
-    const double2_t av = a[j], xv = x[j];
-    s0 = fma(av.x, xv.x, s0);
-    s1 = fma(av.y, (2 * j + 1 < w) ? xv.y : 0.0, s1);
-  }
-  double sum = s0 + s1;
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
-  if (lane == 0) z[row] = sum;
-}
-
-template <int TRSV_RPW>                                // rows per wave of the forward update
-__global__ __launch_bounds__(256) void k_trsv_upd_fwd(const double* __restrict__ Lp, long ldl, long rows,
-                                                      const double* __restrict__ z, double* __restrict__ r) {
-  // Lp: the panel below the block (rows x 512, stride ldl); z: the block's solution (512); r: the rows' residuals
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long row0 = ((long)blockIdx.x * 4 + wv) * TRSV_RPW;
-  if (row0 >= rows) return;
-  double2_t zv[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) zv[k] = reinterpret_cast<const double2_t*>(z)[lane + 64 * k];
-  double2_t av[TRSV_RPW][4];
-#pragma unroll
-  for (int q = 0; q < TRSV_RPW; ++q) {
-    const long row = row0 + q < rows ? row0 + q : rows - 1;     // (clamped: unconditional loads, results of the extra rows dropped)
-    const double2_t* a = reinterpret_cast<const double2_t*>(Lp + row * ldl);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) av[q][k] = a[lane + 64 * k];
-  }
-  double sum[TRSV_RPW];
-#pragma unroll
-  for (int q = 0; q < TRSV_RPW; ++q) {
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { s0 = fma(av[q][k].x, zv[k].x, s0); s1 = fma(av[q][k].y, zv[k].y, s1); }
-    sum[q] = s0 + s1;
-  }
-#pragma unroll
-  for (int q = 0; q < TRSV_RPW; ++q)
-    for (int off = 32; off > 0; off >>= 1) sum[q] += __shfl_down(sum[q], off, 64);
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < TRSV_RPW; ++q)
-      if (row0 + q < rows) r[row0 + q] -= sum[q];
-  }
-}
-
-// (the two transposed products walk DOWN 512 rows per column: with four waves a lane's chain of row loads is eight memory
-//  latencies long -- 9.4 us even for the smallest update; sixteen waves of 32 rows each make it two)
-constexpr int TRSV_BW = 16;                            // waves per workgroup of the backward kernels
-// CW columns per workgroup (64: a lane per column; 16: four row phases inside the wave as well, for the block's own solve
-// and the short updates -- eight workgroups of 256 KB each are bound by what ONE CU can pull from HBM, 8 us a launch)
-template <int CW>
-__device__ __forceinline__ void trsv_colsum(const double* __restrict__ p0, long ld, int row0, int w, const double* s_x,
-                                            double (*s_p)[64], double& out, bool& writer) {
-  // p0: column `cc` of the first row; rows row0 .. w - 1; lane (rp, c): row phase rp of 64 / CW, column c
-  constexpr int RP = 64 / CW, PH = TRSV_BW * RP;       // row phases: per wave, per workgroup
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int rp = lane / CW;
-  double s0 = 0.0, s1 = 0.0;
-  int i = row0 + wv * RP + rp;
-  for (; i + 15 * PH < w; i += 16 * PH) {
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = p0[(long)(i + PH * u) * ld];
-#pragma unroll
-    for (int u = 0; u < 16; u += 2) { s0 = fma(v[u], s_x[i + PH * u], s0); s1 = fma(v[u + 1], s_x[i + PH * (u + 1)], s1); }
-  }
-  for (; i < w; i += PH) s0 = fma(p0[(long)i * ld], s_x[i], s0);
-  s_p[wv][lane] = s0 + s1;
-  __syncthreads();
-  writer = threadIdx.x < CW;
-  double t = 0.0;
-  if (writer) {
-#pragma unroll
-    for (int q = 0; q < TRSV_BW; ++q)
-#pragma unroll
-      for (int h = 0; h < RP; ++h) t += s_p[q][h * CW + lane];
-  }
-  out = t;
-}
-
-template <int CW>
-__global__ __launch_bounds__(1024) void k_trsv_blk_bwd(const double* __restrict__ M, int w, const double* __restrict__ r,
-                                                       double* __restrict__ out) {
-  __shared__ double s_r[CHOL_NB];
-  __shared__ double s_p[TRSV_BW][64];
-  for (int i = threadIdx.x; i < CHOL_NB; i += 64 * TRSV_BW) s_r[i] = i < w ? r[i] : 0.0;
-  __syncthreads();
-  // out[col] = sum_{i >= col} M[i][col] r[i]: the inverse is exactly zero above its diagonal, so the rows start at
-  // the workgroup's first column
-  const int col = blockIdx.x * CW + (threadIdx.x & 63) % CW;
-  const int cc = col < w ? col : w - 1;
-  double t; bool writer;
-  trsv_colsum<CW>(M + cc, CHOL_NB, blockIdx.x * CW, w, s_r, s_p, t, writer);
-  if (writer && col < w) out[col] = t;
-}
-
-template <int CW>
-__global__ __launch_bounds__(1024) void k_trsv_upd_bwd(const double* __restrict__ Lr, long ldl, int w, long cols,
-                                                       const double* __restrict__ a, double* __restrict__ r) {
-  // Lr: the block row (w x cols, stride ldl); a: the block's solution (w); r: the residuals of the columns before it
-  __shared__ double s_a[CHOL_NB];
-  __shared__ double s_p[TRSV_BW][64];
-  for (int i = threadIdx.x; i < CHOL_NB; i += 64 * TRSV_BW) s_a[i] = i < w ? a[i] : 0.0;
-  __syncthreads();
-  const long col = (long)blockIdx.x * CW + (threadIdx.x & 63) % CW;
-  const long cc = col < cols ? col : cols - 1;
-  double t; bool writer;
-  trsv_colsum<CW>(Lr + cc, ldl, 0, w, s_a, s_p, t, writer);
-  if (writer && col < cols) r[col] -= t;
-}
-
-static bool trsv_fast_applies(const double* L, int64_t n, int64_t ldl, const double* inv, const double* x, const int* refine) {
-  static const int on = env_int("DFH_TRSV_FAST", 1);
-  if (!on || (ldl & 1) || ((reinterpret_cast<uintptr_t>(L) | reinterpret_cast<uintptr_t>(inv) | reinterpret_cast<uintptr_t>(x)) & 15)) return false;
-  for (int64_t b = 0; refine && b < (n + CHOL_NB - 1) / CHOL_NB; ++b)
-    if (refine[b] > 0) return false;
-  return true;
-}
-
-// z = L^-1 r (r is used up) -- the forward half
-static int trsv_fast_forward(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const double* inv, double* r, double* z) {
-  const int64_t NB = CHOL_NB;
-  for (int64_t c0 = 0; c0 < n; c0 += NB) {
-    const int64_t w = std::min<int64_t>(NB, n - c0), below = n - c0 - w;
-    hipLaunchKernelGGL(k_trsv_blk_fwd, dim3((unsigned)((w + 3) / 4)), dim3(256), 0, ctx->stream, inv + (c0 / NB) * NB * NB,
-                       (int)w, r + c0, z + c0);
-    DFH_LAUNCH_CHECK();
-    if (below > 4 * NB) {
-      hipLaunchKernelGGL(k_trsv_upd_fwd<8>, dim3((unsigned)((below + 31) / 32)), dim3(256), 0, ctx->stream,
-                         L + (c0 + w) * ldl + c0, (long)ldl, (long)below, z + c0, r + c0 + w);
-      DFH_LAUNCH_CHECK();
-    } else if (below > 0) {                            // a short panel: two rows per wave, four times the workgroups
-      hipLaunchKernelGGL(k_trsv_upd_fwd<2>, dim3((unsigned)((below + 7) / 8)), dim3(256), 0, ctx->stream,
-                         L + (c0 + w) * ldl + c0, (long)ldl, (long)below, z + c0, r + c0 + w);
-      DFH_LAUNCH_CHECK();
-    }
-  }
-  return DFH_OK;
-}
-
-// a = L^-T r (r is used up) -- the backward half
-static int trsv_fast_backward(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const double* inv, double* r, double* a) {
-  const int64_t NB = CHOL_NB, nblk = (n + NB - 1) / NB;
-  for (int64_t b = nblk - 1; b >= 0; --b) {
-    const int64_t c0 = b * NB, w = std::min<int64_t>(NB, n - c0);
-    hipLaunchKernelGGL(k_trsv_blk_bwd<16>, dim3((unsigned)((w + 15) / 16)), dim3(64 * TRSV_BW), 0, ctx->stream, inv + b * NB * NB,
-                       (int)w, r + c0, a + c0);
-    DFH_LAUNCH_CHECK();
-    if (c0 > 0 && c0 < 8 * NB) {                       // fewer than 64 workgroups of 64 columns: 16 columns each
-      hipLaunchKernelGGL(k_trsv_upd_bwd<16>, dim3((unsigned)((c0 + 15) / 16)), dim3(64 * TRSV_BW), 0, ctx->stream, L + c0 * ldl,
-                         (long)ldl, (int)w, (long)c0, a + c0, r);
-      DFH_LAUNCH_CHECK();
-    } else if (c0 > 0) {
-      hipLaunchKernelGGL(k_trsv_upd_bwd<64>, dim3((unsigned)((c0 + 63) / 64)), dim3(64 * TRSV_BW), 0, ctx->stream, L + c0 * ldl,
-                         (long)ldl, (int)w, (long)c0, a + c0, r);
-      DFH_LAUNCH_CHECK();
-    }
-  }
-  return DFH_OK;
-}
-
-// x <- L^-T L^-1 x  (gp_core.py:161-163): the forward half leaves z in a scratch vector, the backward half reads it
-// there and writes alpha to x -- no copy in between
-int trsv_both(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const double* inv, double* x, const int* refine) {
-  if (!trsv_fast_applies(L, n, ldl, inv, x, refine)) {
-    DFH_TRY(trsv_forward(ctx, L, n, ldl, inv, x, refine));
-    return trsv_backward(ctx, L, n, ldl, inv, x, refine);
-  }
-  double* z = nullptr;
-  DFH_TRY(scratch_get(ctx, SCR_VEC3, (size_t)std::max<int64_t>(2 * CHOL_NB, n) * 8, (void**)&z));
-  DFH_TRY(trsv_fast_forward(ctx, L, n, ldl, inv, x, z));
-  return trsv_fast_backward(ctx, L, n, ldl, inv, z, x);
-}
-
-int trsv_forward(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const double* inv,
-                 double* x, const int* refine) {
-  const int64_t NB = CHOL_NB;
-  if (trsv_fast_applies(L, n, ldl, inv, x, refine)) {
-    double* z = nullptr;
-    DFH_TRY(scratch_get(ctx, SCR_VEC3, (size_t)std::max<int64_t>(2 * NB, n) * 8, (void**)&z));
-    DFH_TRY(trsv_fast_forward(ctx, L, n, ldl, inv, x, z));
-    DFH_HIP(hipMemcpyAsync(x, z, (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return DFH_OK;
-  }
-  const int64_t nblk = (n + NB - 1) / NB;
-  const double* diag = inv + nblk * NB * NB;
-  double* tmp = nullptr;
-  DFH_TRY(scratch_get(ctx, SCR_VEC3, (size_t)NB * 8 * 2, (void**)&tmp));
-  double* res = tmp + NB;
-  for (int64_t c0 = 0; c0 < n; c0 += NB) {
-    const int64_t w = (n - c0 < NB) ? n - c0 : NB;
-    const double* Mi = inv + (c0 / NB) * NB * NB;
-    const double* Lbb = diag + (c0 / NB) * NB * NB;
-    // x_i <- Linv_ii x_i
-    DFH_TRY(gemv_rows(ctx, Mi, w, w, NB, x + c0, 1.0, nullptr, 0.0, tmp));
-    for (int s = 0; s < (refine ? refine[c0 / NB] : 0); ++s) {
-      // res = b_i - L_ii x ; x += Linv_ii res
-      DFH_TRY(gemv_rows(ctx, Lbb, w, w, NB, tmp, -1.0, x + c0, 1.0, res, true));
-      DFH_TRY(gemv_rows(ctx, Mi, w, w, NB, res, 1.0, tmp, 1.0, tmp));
-    }
-    DFH_HIP(hipMemcpyAsync(x + c0, tmp, (size_t)w * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    // x[i+1:] <- x[i+1:] - L[i+1:, i] x_i
-    const int64_t below = n - c0 - w;
-    if (below > 0)
-      DFH_TRY(gemv_rows(ctx, L + (c0 + w) * ldl + c0, below, w, ldl, x + c0, -1.0, x + c0 + w, 1.0, x + c0 + w));
-  }
-  return DFH_OK;
-}
-
-int trsv_backward(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const double* inv,
-                  double* x, const int* refine) {
-  const int64_t NB = CHOL_NB;
-  if (trsv_fast_applies(L, n, ldl, inv, x, refine)) {
-    double* a = nullptr;
-    DFH_TRY(scratch_get(ctx, SCR_VEC3, (size_t)std::max<int64_t>(2 * NB, n) * 8, (void**)&a));
-    DFH_TRY(trsv_fast_backward(ctx, L, n, ldl, inv, x, a));
-    DFH_HIP(hipMemcpyAsync(x, a, (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return DFH_OK;
-  }
-  const int64_t nblk = (n + NB - 1) / NB;
-  const double* diag = inv + nblk * NB * NB;
-  double* tmp = nullptr;
-  DFH_TRY(scratch_get(ctx, SCR_VEC3, (size_t)NB * 8 * 2, (void**)&tmp));
-  double* res = tmp + NB;
-  for (int64_t b = nblk - 1; b >= 0; --b) {
-    const int64_t c0 = b * NB;
-    const int64_t w = (n - c0 < NB) ? n - c0 : NB;
-    const double* Mi = inv + b * NB * NB;
-    const double* Lbb = diag + b * NB * NB;
-    // x_i <- Linv_ii^T x_i
-    DFH_TRY(gemv_cols(ctx, Mi, w, w, NB, x + c0, 1.0, nullptr, 0.0, tmp));
-    for (int s = 0; s < (refine ? refine[b] : 0); ++s) {
-      // res = b_i - L_ii^T x ; x += Linv_ii^T res
-      DFH_TRY(gemv_cols(ctx, Lbb, w, w, NB, tmp, -1.0, x + c0, 1.0, res));
-      DFH_TRY(gemv_cols(ctx, Mi, w, w, NB, res, 1.0, tmp, 1.0, tmp));
-    }
-    DFH_HIP(hipMemcpyAsync(x + c0, tmp, (size_t)w * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    // x[:i] <- x[:i] - L[i, :i]^T x_i
-    if (c0 > 0) DFH_TRY(gemv_cols(ctx, L + c0 * ldl, w, c0, ldl, x + c0, -1.0, x, 1.0, x));
-  }
-  return DFH_OK;
-}
-
-// residual buffer of the refined row solves (m x NB), only when some block takes a step
-static int refine_scratch(dfh_ctx* ctx, const int* refine, int64_t nblk, int64_t m, double** out) {
-  *out = nullptr;
-  bool any = false;
-  for (int64_t b = 0; refine && b < nblk; ++b) any = any || refine[b] > 0;
-  if (any) DFH_TRY(scratch_get(ctx, SCR_REFINE, (size_t)m * CHOL_NB * 8, (void**)out));
-  return DFH_OK;
-}
-
-// at most this many right-hand rows take the right-looking (wide, shallow) form of trsm_rows
-constexpr int64_t TRSM_FEW_ROWS = 256;
-
-int trsm_rows(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const double* inv,
-              double* Kct, int64_t m, int64_t ldk, const int* refine, const double* diag_override) {
-  if (m <= 0 || n <= 0) return DFH_OK;
-  const int64_t NB = CHOL_NB;
-  const double* diag = diag_override ? diag_override : inv + ((n + NB - 1) / NB) * NB * NB;      // clean copies of the diagonal blocks
-  double *T = nullptr, *R2 = nullptr;
-  DFH_TRY(scratch_get(ctx, SCR_TMP, (size_t)m * NB * 8, (void**)&T));
-  DFH_TRY(refine_scratch(ctx, refine, (n + NB - 1) / NB, m, &R2));
-  if (m <= TRSM_FEW_ROWS) {
-    // A handful of rows (single-point GP.eval calls, tree-search frontiers, hallucinated batches):
-    // the left-looking form below would run each block as ONE tile row with a K loop over every
-    // earlier column -- a few workgroups walking all of L serially.  Right-looking instead: solve
-    // the block, then subtract its contribution from ALL later columns at once, a GEMM that is
-    // (n - c0) / 128 tiles wide with K = 512, so L streams from HBM across the whole chip.
-    for (int64_t c0 = 0; c0 < n; c0 += NB) {
-      const int64_t w = (n - c0 < NB) ? n - c0 : NB;
-      const int64_t rest = n - c0 - w;
-      const double* Linv = inv + (c0 / NB) * NB * NB;
-      const double* Lpanel = L + (c0 + w) * ldl + c0;
-      // (the inverse block has an exactly zero upper part, so the full K range gives the same sum)
-      // the solved block goes to T (a GEMM may not overwrite what other workgroups still read) and
-      // has to end up in place as well: the few-row update below stages T anyway and writes the
-      // copy on the side; only the last block, which has nothing to update, needs a copy launch
-      const bool skinny_update = rest > 0 && gemm_skinny_applies(m, rest, w, T, NB, Lpanel, ldl) && (ldk % 2) == 0;
-      if (gemm_skinny_applies(m, w, w, Kct + c0, ldk, Linv, NB))
-        DFH_TRY(gemm_skinny_nt(ctx, m, w, w, 1.0, Kct + c0, ldk, Linv, NB, 0.0, nullptr, 0, T, NB));
-      else
-        DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, 1.0, Kct + c0, ldk, Linv, NB, 0.0, nullptr, 0, T, NB));
-      for (int s = 0; s < (refine ? refine[c0 / NB] : 0); ++s) {
-        // R <- B - X L_bb^T from the untouched right-hand side (it is only overwritten by the solution
-        // below) ; X <- X + R Linv^T.  (Round 2 kept the residual IN PLACE of the right-hand side, which
-        // is right for one step only: the second would subtract X0 L^T twice.)
-        const double* Lbb = diag + (c0 / NB) * NB * NB;
-        DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, -1.0, T, NB, Lbb, NB, 1.0, Kct + c0, ldk, R2, NB));
-        DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, 1.0, R2, NB, Linv, NB, 1.0, T, NB, T, NB));
-      }
-      if (skinny_update) {
-        DFH_TRY(gemm_skinny_nt(ctx, m, rest, w, -1.0, T, NB, Lpanel, ldl, 1.0, Kct + c0 + w, ldk,
-                               Kct + c0 + w, ldk, Kct + c0, ldk));
-      } else {
-        DFH_TRY(copy_matrix(ctx, T, NB, Kct + c0, ldk, m, w));
-        if (rest > 0)
-          DFH_TRY(gemm_f64(ctx, 0, m, rest, w, -1.0, T, NB, Lpanel, ldl, 1.0, Kct + c0 + w, ldk,
-                           Kct + c0 + w, ldk));
-      }
-    }
-    return DFH_OK;
-  }
-  for (int64_t c0 = 0; c0 < n; c0 += NB) {
-    const int64_t w = (n - c0 < NB) ? n - c0 : NB;
-    // T = Kct[:, c0:c0+w] - Vt[:, 0:c0] * L[c0:c0+w, 0:c0]^T      (K = 0 degenerates to a copy)
-    DFH_TRY(gemm_f64(ctx, 0, m, w, c0, -1.0, Kct, ldk, L + c0 * ldl, ldl, 1.0, Kct + c0, ldk, T, NB));
-    // Vt[:, c0:c0+w] = T * Linv_ii^T
-    const double* Linv = inv + (c0 / NB) * NB * NB;
-    DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, 1.0, T, NB, Linv, NB, 0.0, nullptr, 0, Kct + c0, ldk));
-    for (int s = 0; s < (refine ? refine[c0 / NB] : 0); ++s) {
-      // R <- T - X L_bb^T (the residual of the right-hand side T, which stays) ; X <- X + R Linv^T
-      const double* Lbb = diag + (c0 / NB) * NB * NB;
-      DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, -1.0, Kct + c0, ldk, Lbb, NB, 1.0, T, NB, R2, NB));
-      DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, 1.0, R2, NB, Linv, NB, 1.0, Kct + c0, ldk, Kct + c0, ldk));
-    }
-  }
-  return DFH_OK;
-}
-
 int tri_block_inverses(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, double* inv, int* refine_out,
                        double* diag) {
   const int64_t NB = CHOL_NB;
@@ -2602,142 +1644,6 @@ int tri_block_inverses(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, do
   return DFH_OK;
 }
 
-int trsm_rows_backward(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const double* inv,
-                       double* Bt, int64_t m, int64_t ldb, const int* refine) {
-  if (m <= 0 || n <= 0) return DFH_OK;
-  const int64_t NB = CHOL_NB;
-  const double* diag = inv + ((n + NB - 1) / NB) * NB * NB;
-  double *T = nullptr, *R2 = nullptr;
-  DFH_TRY(scratch_get(ctx, SCR_TMP, (size_t)m * NB * 8, (void**)&T));
-  const int64_t nblk = (n + NB - 1) / NB;
-  DFH_TRY(refine_scratch(ctx, refine, nblk, m, &R2));
-  for (int64_t b = nblk - 1; b >= 0; --b) {
-    const int64_t c0 = b * NB;
-    const int64_t w = (n - c0 < NB) ? n - c0 : NB;
-    const int64_t below = n - c0 - w;
-    // T = Bt[:, c0:c0+w] - Xt[:, c0+w:] * L[c0+w:, c0:c0+w]
-    DFH_TRY(gemm_f64(ctx, GEMM_TRANSB, m, w, below, -1.0, Bt + c0 + w, ldb, L + (c0 + w) * ldl + c0, ldl,
-                     1.0, Bt + c0, ldb, T, NB));
-    // Xt[:, c0:c0+w] = T * Linv_ii
-    DFH_TRY(gemm_f64(ctx, GEMM_TRANSB, m, w, w, 1.0, T, NB, inv + b * NB * NB, NB, 0.0, nullptr, 0,
-                     Bt + c0, ldb));
-    for (int s = 0; s < (refine ? refine[b] : 0); ++s) {
-      // R <- T - X L_bb (the residual of the right-hand side T, which stays) ; X <- X + R Linv
-      DFH_TRY(gemm_f64(ctx, GEMM_TRANSB, m, w, w, -1.0, Bt + c0, ldb, diag + b * NB * NB, NB, 1.0, T, NB, R2, NB));
-      DFH_TRY(gemm_f64(ctx, GEMM_TRANSB, m, w, w, 1.0, R2, NB, inv + b * NB * NB, NB, 1.0, Bt + c0, ldb, Bt + c0, ldb));
-    }
-  }
-  return DFH_OK;
-}
-
-// Launch of lml_wg_kernel: `count` candidates, one workgroup each (K: padded matrices of order 64 * ceil((n + 1) / 64),
-// see the kernel).  d_par: [count] augmented diagonal entries, then [count] prior means; d_out2: [count][2];
-// d_info: [count] failing pivots (zeroed here).  Asynchronous on ctx->stream.
-// team > 1: `team` workgroups per candidate (lml_team_kernel; team * count should not exceed the CUs).  d_status
-// (device, 8 bytes, or null when team == 1) is zeroed here and non-zero afterwards iff a hand-off wait expired:
-// the results of the launch are then void.
-int lml_wg_batch(dfh_ctx* ctx, double* K, int64_t sK, int64_t ld, int64_t n, int count, const double* d_y,
-                 const double* d_par, double* d_out2, long long* d_info, int team, unsigned long long* d_status,
-                 int* d_sync_zeroed) {
-  // d_sync_zeroed: the team's flags ([count][LMLT_SYNC_INTS]) in a block the caller has ALREADY zeroed together with
-  // d_info and d_status (one memset per group instead of three); null: allocated and zeroed here.
-  static_assert(LMLT_SYNC_INTS == LMLT_SYNC_INTS_PER_CANDIDATE, "common.h and chol.hip disagree on the flags per candidate");
-  DFH_ARG(ctx && K && d_y && d_par && d_out2 && d_info && n >= 1 && n <= LMLWG_MAX_N && count >= 1 && team >= 1 &&
-          team <= 32 && (team == 1 || d_status));
-  const int64_t nbt = (n + 1 + PB - 1) / PB;
-  DFH_ARG(ld >= nbt * PB && (ld & 1) == 0 && sK >= nbt * PB * ld && (reinterpret_cast<uintptr_t>(K) & 15) == 0);
-  static bool attr_set_dev[DFH_MAX_DEVICES] = {false};
-  bool& attr_set = attr_set_dev[ctx->device];
-  if (!attr_set) {
-    DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lml_wg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                DIAG_STEP_SMEM));
-    DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lml_team_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                LMLT_SMEM));
-    attr_set = true;
-  }
-  if (!d_sync_zeroed) DFH_HIP(hipMemsetAsync(d_info, 0, (size_t)count * 8, ctx->stream));
-  LmlWgArgs a;
-  a.K = K; a.sK = (long)sK; a.ld = (long)ld; a.n = (int)n; a.nbt = (int)nbt;
-  a.y = d_y; a.par = d_par; a.count = count; a.out2 = d_out2; a.info = d_info;
-  a.T = team; a.sync = nullptr; a.linvbuf = nullptr; a.status = d_status; a.spin_limit = 0;
-  if (team == 1) {
-    hipLaunchKernelGGL(lml_wg_kernel, dim3((unsigned)count), dim3(256), DIAG_STEP_SMEM, ctx->stream, a);
-    DFH_LAUNCH_CHECK();
-    return DFH_OK;
-  }
-  DFH_TRY(scratch_get(ctx, SCR_CHOLINV, (size_t)count * nbt * LMLT_LINV * 8, (void**)&a.linvbuf));
-  if (d_sync_zeroed) {
-    a.sync = d_sync_zeroed;
-  } else {
-    DFH_TRY(scratch_get(ctx, SCR_CHOLSYNC, (size_t)count * LMLT_SYNC_INTS * sizeof(int), (void**)&a.sync));
-    DFH_HIP(hipMemsetAsync(a.sync, 0, (size_t)count * LMLT_SYNC_INTS * sizeof(int), ctx->stream));
-    DFH_HIP(hipMemsetAsync(d_status, 0, 8, ctx->stream));
-  }
-  // a legitimate wait lasts well under a millisecond; a poll is ~1 us: give up after ~0.1 s (DFH_TEST_SPIN_LIMIT=0: at once, the fallback's test)
-  static const int spin_limit = env_int("DFH_TEST_SPIN_LIMIT", 1 << 17);
-  a.spin_limit = spin_limit;
-#ifdef DFH_DEBUG_HOOKS
-  a.stamps = g_lmlt_stamps;
-#endif
-  hipLaunchKernelGGL(lml_team_kernel, dim3((unsigned)(count * team)), dim3(256), LMLT_SMEM, ctx->stream, a);
-  DFH_LAUNCH_CHECK();
-  return DFH_OK;
-}
-
-bool lml_wg_fused_applies(const KernDev* kds, int count, int64_t n) {
-  static const int fused_max = env_int("DFH_LML_FUSED", 16);       // candidates per call; 0: off
-  static const int max_n = std::min(255, env_int("DFH_LML_FUSED_MAX_N", (int)LMLF_MAX_N));
-  if (count < 1 || count > fused_max || n < 1 || n > max_n) return false;
-  for (int c = 0; c < count; ++c)
-    if (kds[c].P > TINY_MAX_P || kds[c].n_parts > TINY_MAX_PARTS || kds[c].P < 1 || !kds[c].stationary || kds[c].esp ||
-        n * (int64_t)(kds[c].P + kds[c].n_parts) > LMLF_LDS_DOUBLES) return false;
-  return true;
-}
-
-int lml_wg_fused_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double* dX, int64_t n, int64_t ldx,
-                       const double* y_host, const double* noise_vars, const double* mean_consts,
-                       double* logdet_dot, long long* info) {
-  DFH_ARG(ctx && kds && dX && y_host && noise_vars && logdet_dot && info && lml_wg_fused_applies(kds, count, n));
-  const int64_t nbt = (n + 1 + PB - 1) / PB, NP = PB * nbt, sK = NP * NP;
-  static bool attr_set_dev[DFH_MAX_DEVICES] = {false};
-  if (!attr_set_dev[ctx->device]) {
-    DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lml_wgf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                DIAG_STEP_SMEM));
-    attr_set_dev[ctx->device] = true;
-  }
-  TinyBlob tb;
-  DFH_TRY(tiny_blob_build(ctx, kds, count, n, y_host, noise_vars, mean_consts, &tb));
-  double *Kb = nullptr, *ybuf = nullptr;
-  DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)count * sK * 8, (void**)&Kb));
-  DFH_TRY(scratch_get(ctx, SCR_VEC, (size_t)std::max<int64_t>(256, n * 8), (void**)&ybuf));
-  LmlWgArgs a;
-  a.K = Kb; a.sK = (long)sK; a.ld = (long)NP; a.n = (int)n; a.nbt = (int)nbt;
-  a.y = ybuf; a.par = nullptr; a.count = count; a.out2 = nullptr; a.info = nullptr;
-  a.T = 1; a.sync = nullptr; a.linvbuf = nullptr; a.status = nullptr; a.spin_limit = 0;
-  LmlFuse f;
-  f.ec = kExpConsts;
-  f.X = dX; f.ldx = (long)ldx;
-  f.blob = tb.host; f.y_off = (long)tb.y_off;
-  f.ybuf = ybuf; f.out4 = tb.res; f.direct = 1;
-  volatile double* vres = tb.res;
-  for (int c = 0; c < count; ++c) vres[4 * c + 3] = -1.0;          // "not there yet"
-  hipLaunchKernelGGL(lml_wgf_kernel, dim3((unsigned)count), dim3(256), DIAG_STEP_SMEM, ctx->stream, a, f);
-  DFH_LAUNCH_CHECK();
-  DFH_TRY(tiny_poll_results(ctx, vres, count, "lml_wgf_kernel"));
-  for (int c = 0; c < count; ++c) {
-    logdet_dot[2 * c] = vres[4 * c];
-    logdet_dot[2 * c + 1] = vres[4 * c + 1];
-    info[c] = (long long)vres[4 * c + 2];
-    if (info[c] == 0 && (!std::isfinite(logdet_dot[2 * c]) || !std::isfinite(logdet_dot[2 * c + 1]))) info[c] = -2;
-  }
-  return DFH_OK;
-}
-
-#ifdef DFH_DEBUG_HOOKS
-// Diagnostics: the team kernel's next launches stamp their progress into `dev_buf` (device, [workgroups][32][16] int64,
-// zeroed by the caller); null switches it off.  tools/dbg_lmlt.py decodes the stamps.
-extern "C" int dfh_debug_lmlt_stamps(void* dev_buf) { g_lmlt_stamps = reinterpret_cast<long long*>(dev_buf); return DFH_OK; }
-#endif
 #ifdef DFH_DEBUG_HOOKS      // diagnostics: built only with `python -m dragonfly_amd.build --debug-hooks` (include/dfhip_debug.h)
 // Diagnostics hook (not part of the product path): times `reps` back-to-back launches of the
 // 64-wide diagonal step on a synthetic SPD block and returns in-kernel cycle stamps.
@@ -2828,7 +1734,7 @@ extern "C" int dfh_debug_panel_stamps(dfh_ctx* ctx, int reps, int rows_below, do
     fa.strideD = 0; fa.strideL = 0; fa.strideI = 0;
     fa.status = reinterpret_cast<unsigned long long*>(d_info + CHOL_MAX_BATCH + 8); fa.spin_limit = SPIN_LIMIT_DEFAULT;
     fa.resident = nullptr; fa.wait_ptr = nullptr; fa.wait_target = 0;
-    fa.prog_sleep = env_int("DFH_CHOL_PROG_SLEEP", 8);
+    fa.prog_sleep = chol_switches().prog_sleep;
     fa.stamps = d_st;
     DFH_HIP(hipEventRecord(e0, S));
     hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)nwg, 1), dim3(256), FUSED_SMEM, S, fa);

@@ -294,8 +294,9 @@ int kerndev_build(dfh_ctx* ctx, const dfh_kernel_desc* k, KernDev* out);
 int kerndev_build_host(const dfh_kernel_desc* k, KernDev* out);
 int kerndev_stage_many(KernDev* kds, int count, char* host, void* d_blob, size_t blob_bytes);
 size_t kerndev_blob_bytes(const KernDev& kd);
+void kerndev_blob_fill(const KernDev& kd, char* host);     // the image itself, kerndev_blob_bytes(kd) bytes at host
 int kerndev_upload_many(dfh_ctx* ctx, KernDev* kds, int count, void* d_blob, size_t blob_bytes);
-// One-launch tuning objective for small problems (kernmat.hip: k_lml_tiny): applies when
+// One-launch tuning objective for small problems (lml_tiny.hip: k_lml_tiny): applies when
 // n <= TINY_MAX_N and every candidate's packed width / part count fits the LDS budget.
 constexpr int64_t TINY_MAX_N = 128;
 constexpr int64_t TINY64_MAX_N = 63;      // k_lml_tiny64: the system (n + 1 rows) is one 64 x 64 tile
@@ -312,7 +313,7 @@ int tiny_blob_build(dfh_ctx* ctx, const KernDev* kds, int count, int64_t n, cons
                     const double* noise_vars, const double* mean_consts, TinyBlob* tb);
 int tiny_poll_results(dfh_ctx* ctx, volatile double* vres, int count, const char* what);
 // TINY64_MAX_N < n <= LMLF_MAX_N, a handful of candidates: Gram matrix, factorisation and forward solve of each candidate in ONE
-// launch by one workgroup (chol.hip: lml_wgf_kernel), descriptors and results through the pinned buffer.
+// launch by one workgroup (lml_wg.h: lml_wgf_kernel), descriptors and results through the pinned buffer.
 // info[c]: 0 = logdet_dot[2c], [2c+1] are valid; otherwise the candidate is for the lock-step schedule (a failed pivot:
 // the ladder; no noise: nothing bounds the augmented pivot).
 constexpr int64_t LMLF_MAX_N = 128;     // (beyond, the team schedule -- one copy up, one memset, one copy back per group since round 6 -- is as fast: 101 us
@@ -388,7 +389,7 @@ int stable_cholesky_device(dfh_ctx* ctx, double* A, int64_t n, double* keep_inv,
 constexpr int DFH_INTERNAL_RETRY = 1000;   // chol.hip internal: never crosses the C-ABI (a hand-off wait expired)
 constexpr int DFH_INTERNAL_RETRY_COND = 1001;   // ... a block inverse too poor for the inverse-based panel solve (deterministic)
 
-// The tuning objective of `count` candidates, one workgroup per candidate (chol.hip: lml_wg_kernel): Cholesky of the
+// The tuning objective of `count` candidates, one workgroup per candidate (lml_wg.h: lml_wg_kernel): Cholesky of the
 // augmented matrix [[K, .], [(y - m)^T, c]] of each, sum(log L_ii) and |L^-1 (y - m)|^2 out.  K: matrices padded to
 // order 64 * ceil((n + 1) / 64) (only the n x n part has to be filled), sK doubles apart, row stride ld.
 constexpr int64_t LMLWG_MAX_N = 2047;
@@ -397,7 +398,7 @@ constexpr int64_t LMLWG_MAX_N = 2047;
 int lml_wg_batch(dfh_ctx* ctx, double* K, int64_t sK, int64_t ld, int64_t n, int count, const double* d_y,
                  const double* d_par, double* d_out2, long long* d_info, int team = 1,
                  unsigned long long* d_status = nullptr, int* d_sync_zeroed = nullptr);
-constexpr int LMLT_SYNC_INTS_PER_CANDIDATE = 64;     // (= chol.hip's LMLT_SYNC_INTS: flags of a team, per candidate)
+constexpr int LMLT_SYNC_INTS = 64;     // flags of a team, per candidate (lml_wg.h: diag[j], then brow[j]); a caller that passes d_sync_zeroed sizes it with this
 
 // alpha-solves with the factor and its diagonal-block inverses (in place on x[n]):
 //   forward : x <- L^{-1} x          backward : x <- L^{-T} x

@@ -1,10 +1,28 @@
-// The 64 x 64 pivot-block factorisation by the four waves of a workgroup (factor64_waves) and its helpers.
-// Shared by chol.hip (diagonal steps, one-launch panels, the one-workgroup tuning objective) and kernmat.hip (the
-// whole tuning objective of a small problem in one launch).  Include inside the translation unit's anonymous namespace.
+// The 64 x 64 pivot-block factorisation by the four waves of a workgroup (factor64_waves) and its helpers, and the
+// constants its users share.  Shared by chol.hip (diagonal steps, one-launch panels), lml_wg.h (the one-workgroup /
+// team tuning objective) and lml_tiny.hip (the whole tuning objective of a small problem in one launch).  Include inside
+// the translation unit's anonymous namespace.
 #pragma once
 
 constexpr int PB = 64;       // pivot block
+[[maybe_unused]] constexpr int PBP = 65;      // LDS row stride
+// row stride of the staged pivot block and of the column-permuted factor image made from it (16-byte aligned rows)
+constexpr int SPP = 66;
+// dynamic LDS of diag_step64_kernel and of the one-workgroup tuning kernels, which run its row solve on the same images
+[[maybe_unused]] constexpr int DIAG_STEP_SMEM = (PB * SPP + PB * PBP + PB + PB * PB + 3 * PB * 17 + 8 * 16 * 17) * 8;   // image, panel rows, rdiag, ring, layout buffers, 16-blocks + inverses
+
+// Hand-off status word of a factorisation (d_info[CHOL_MAX_BATCH + 8], zeroed per call): set when a
+// bounded wait expired.  The host then repeats the factorisation on the schedule without
+// inter-workgroup hand-offs (cholesky_device), or reports DFH_ERR_HIP when the input is gone.
 constexpr unsigned SYNC_ST_RING = 1;      // an LDS column ring flag never came up (factor64_waves)
+[[maybe_unused]] constexpr unsigned SYNC_ST_FUSED = 2;     // a strip of the one-launch panel waited too long for another strip
+[[maybe_unused]] constexpr unsigned SYNC_ST_GATE = 4;      // a gate kernel / resident diagonal kernel waited too long for another launch
+// How many polls a bounded wait takes before it gives up; DFH_TEST_SPIN_LIMIT replaces both (0: every wait expires at
+// once, the fallbacks' test).  Two defaults on purpose.  The factorisation's waits (panel strips, gates, the resident
+// diagonal block) may legitimately last as long as a trailing update of a large matrix:
+[[maybe_unused]] constexpr int SPIN_LIMIT_DEFAULT = 1 << 21;   // polls of ~0.5 us each: a second, a few hundred times the longest legitimate wait
+// the team kernel's waits are for a neighbour's 64-column step of a matrix of at most 2047 rows:
+[[maybe_unused]] constexpr int LMLT_SPIN_LIMIT_DEFAULT = 1 << 17;   // a legitimate wait lasts well under a millisecond; a poll is ~1 us: give up after ~0.1 s
 
 // ---------------------------------------------------------------------------------------------
 // 64 x 64 pivot-block kernels.  The block is factored by the four waves of a workgroup without
@@ -87,7 +105,6 @@ __device__ __forceinline__ void fast_rsqrt_sqrt(double d, double* rs, double* sq
 // Branch-free: a non-positive / NaN pivot only raises a flag (columns and flags are still
 // published, so nobody waits forever).
 #define COMPILER_BARRIER() asm volatile("" ::: "memory")
-constexpr int SPP_STAGE = 66;   // row stride of the staged pivot block (= SPP of the factor image, below)
 
 // Owner step for column k = 16 w + KL.  The published ring slot of column k holds u[i][k] for the
 // rows i >= 1 and, in row 0's place, 1/d_k (row 0 of a column k >= 1 lies above the diagonal and
@@ -260,7 +277,7 @@ __device__ __forceinline__ int factor64_waves(double (&a)[16], int lane, int w, 
   int bad = -1;
   if (w == 0) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) a[j] = stage[lane * SPP_STAGE + j];       // lane <- row, columns 0..15
+    for (int j = 0; j < 16; ++j) a[j] = stage[lane * SPP + j];       // lane <- row, columns 0..15
     __syncthreads();                                   // the staged block is read: its LDS may be reused
   } else {
     double4_t acc[4];
@@ -268,7 +285,7 @@ __device__ __forceinline__ int factor64_waves(double (&a)[16], int lane, int w, 
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[t][r] = stage[(16 * t + kq + 4 * r) * SPP_STAGE + 16 * w + l15];
+      for (int r = 0; r < 4; ++r) acc[t][r] = stage[(16 * t + kq + 4 * r) * SPP + 16 * w + l15];
     __syncthreads();
     for (int kb = 0; kb < w; ++kb) f64_consume_block(acc, lane, w, kb, ring, ring_timeout);
     // accumulator layout -> row per lane, through this wave's private LDS block
@@ -350,7 +367,7 @@ __device__ __forceinline__ int tiny64_factor(double (&a)[16], int lane, int w, c
   const bool active = 16 * w <= klast;                 // wave-uniform
   if (w == 0) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) a[j] = stage[lane * SPP_STAGE + j];
+    for (int j = 0; j < 16; ++j) a[j] = stage[lane * SPP + j];
     __syncthreads();
   } else {
     double4_t acc[4];
@@ -358,7 +375,7 @@ __device__ __forceinline__ int tiny64_factor(double (&a)[16], int lane, int w, c
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[t][r] = stage[(16 * t + kq + 4 * r) * SPP_STAGE + 16 * w + l15];
+      for (int r = 0; r < 4; ++r) acc[t][r] = stage[(16 * t + kq + 4 * r) * SPP + 16 * w + l15];
     __syncthreads();
     if (!active) return -1;
     for (int kb = 0; kb < w; ++kb) f64_consume_block(acc, lane, w, kb, ring, ring_timeout);

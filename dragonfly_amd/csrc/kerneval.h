@@ -1,7 +1,7 @@
 // Kernel evaluation on the device: exp / sqrt for the arguments a stationary kernel produces, one part's value from a
 // squared distance (kern_eval), the polynomial / exponential-decay / Hamming parts, the combination rule of a product kernel with
-// additive factors, NumPy's pairwise row sum of squares.  Shared by kernmat.hip (the kernel-matrix kernels, the tuning
-// objective of small problems) and chol.hip (the one-workgroup tuning objective with its Gram matrix built in the same
+// additive factors, NumPy's pairwise row sum of squares.  Shared by kernmat.hip (the kernel-matrix kernels), lml_tiny.hip (the tuning
+// objective of small problems) and lml_wg.h (the one-workgroup tuning objective with its Gram matrix built in the same
 // launch).  Include inside the translation unit's anonymous namespace.
 #pragma once
 
@@ -234,7 +234,7 @@ __device__ __forceinline__ void tiny_publish(double* out, bool direct, double v0
 
 // The lower triangle of a small Gram matrix K (the caller's store adds what belongs on the diagonal) from scaled inputs in LDS (Xp [n][P], Np [n][n_parts]), by the
 // 256 threads of a workgroup; store(i, j, value) for j <= i < n.  The triangle is walked as a rectangle: row p and row
-// n - 1 - p together hold n + 1 entries.  (k_lml_tiny64 and the fused tuning objective of chol.hip, round 6.)
+// n - 1 - p together hold n + 1 entries.  (k_lml_tiny64 and the fused tuning objective of lml_wg.h, round 6.)
 // A single SE or Matern (nu <= 2.5) part -- the commonest candidates -- takes four entries per thread at a time: such a workgroup runs one wave
 // per SIMD, nothing hides the latency of an entry's chain (index division -> LDS -> dot product -> twelve dependent FMAs
 // of the exponential, ~850 cycles), so four independent chains in flight are worth a factor of two to three.  The

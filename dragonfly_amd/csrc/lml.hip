@@ -1,5 +1,5 @@
 // The tuning objective, extern "C" dfh_gp_lml_batch: its dispatcher, the workgroup-per-candidate and lock-step schedules,
-// and the kernels of the lock-step schedule's solve stage (the one-launch forms live in kernmat.hip and chol.hip).
+// and the kernels of the lock-step schedule's solve stage (the one-launch forms live in lml_tiny.hip and lml_wg.h).
 #include "common.h"
 #include <cstring>
 #include <math.h>
@@ -393,7 +393,7 @@ int redo_alone(const LmlCall& a, int c) {
   return lml_batch_lockstep(one);
 }
 
-// One workgroup per candidate (chol.hip: lml_wg_kernel), 128 < n <= LMLWG_MAX_N: per group of up to one candidate
+// One workgroup per candidate (lml_wg.h: lml_wg_kernel), 128 < n <= LMLWG_MAX_N: per group of up to one candidate
 // per CU three launches -- pack, Gram matrices, factor + forward solve + reductions -- and one copy back.  A
 // candidate whose matrix does not factor as it stands (or whose augmented pivot fails) is handed to the
 // lock-step schedule on its own, which runs the stable_cholesky ladder exactly as before.
@@ -440,7 +440,7 @@ int lml_batch_wg(const LmlCall& a) {
   // back and three synchronisations per group -- 160 of a small group's 210 us, profiles/r06_small_calls.txt.)
   double *Kb = nullptr, *ctl = nullptr;
   DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)G * sK * 8, (void**)&Kb));
-  const size_t ctl_bytes = (size_t)(3 * G + 8) * 8 + (size_t)G * LMLT_SYNC_INTS_PER_CANDIDATE * sizeof(int);
+  const size_t ctl_bytes = (size_t)(3 * G + 8) * 8 + (size_t)G * LMLT_SYNC_INTS * sizeof(int);
   DFH_TRY(scratch_get(ctx, SCR_LMLCTL, ctl_bytes, (void**)&ctl));
   std::vector<KernDev> kds((size_t)G);
   std::vector<char> skip((size_t)G, 0);
@@ -485,7 +485,7 @@ int lml_batch_wg(const LmlCall& a) {
       if (skip[c]) hpar[c] = 1.0;
     }
     DFH_HIP(hipMemcpyAsync(blob, hup, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    // a group that leaves most of the device idle gets a TEAM of workgroups per candidate (chol.hip: lml_team_kernel)
+    // a group that leaves most of the device idle gets a TEAM of workgroups per candidate (lml_wg.h: lml_team_kernel)
     int team = 1;
     // (a timed-out hand-off costs ~0.1 s of polling plus the rebuilt group, and a slice sampler calls a hundred thousand
     //  times: after one, the context's next 32 groups take one workgroup per candidate -- a shared device does not pay
@@ -504,7 +504,7 @@ int lml_batch_wg(const LmlCall& a) {
       {
         SectionTimer t(ctx, DFH_T_CHOL);
         // failed pivots, status and the team's flags: one memset (the results in front of them are always written)
-        DFH_HIP(hipMemsetAsync(dinfo, 0, (size_t)(g + 1) * 8 + (tm > 1 ? (size_t)g * LMLT_SYNC_INTS_PER_CANDIDATE * sizeof(int) : 0),
+        DFH_HIP(hipMemsetAsync(dinfo, 0, (size_t)(g + 1) * 8 + (tm > 1 ? (size_t)g * LMLT_SYNC_INTS * sizeof(int) : 0),
                                ctx->stream));
         DFH_TRY(lml_wg_batch(ctx, Kb, sK, NP, n, g, dy, dpar, red, dinfo, tm, d_status, d_sync));
       }
@@ -575,7 +575,7 @@ extern "C" int dfh_gp_lml_batch(dfh_ctx* ctx, const dfh_kernel_desc* descs, int3
     for (int c = 0; c < nb; ++c) DFH_TRY(kerndev_build_host(&descs[c], &all[c]));
     if (fused_range && lml_wg_fused_applies(all.data(), nb, n)) {
       // a handful of mid-sized candidates (a slice sampler's call at 64 <= n <= 128): Gram matrix, factorisation and
-      // forward solve of each in ONE launch by one workgroup, nothing copied (chol.hip: lml_wgf_kernel)
+      // forward solve of each in ONE launch by one workgroup, nothing copied (lml_wg.h: lml_wgf_kernel)
       std::vector<double> ld_dot((size_t)nb * 2);
       std::vector<long long> info((size_t)nb);
       DFH_TRY(labels_on_host(ctx, y, n, flags, y_hold, &y_host));
@@ -595,7 +595,7 @@ extern "C" int dfh_gp_lml_batch(dfh_ctx* ctx, const dfh_kernel_desc* descs, int3
     }
     if (tiny_range && lml_tiny_applies(all.data(), nb, n)) {
       // small problems: pack, Gram matrix, stable_cholesky and the solve of every candidate in ONE
-      // launch (kernmat.hip: k_lml_tiny)
+      // launch (lml_tiny.hip: k_lml_tiny)
       std::vector<double> ld_dot((size_t)nb * 2);
       DFH_TRY(labels_on_host(ctx, y, n, flags, y_hold, &y_host));
       SectionTimer t(ctx, DFH_T_CHOL);

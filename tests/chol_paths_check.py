@@ -1,7 +1,18 @@
 """Run in a subprocess by tests/test_gpu_chol_paths.py with the factorisation's schedule switches set
 in the environment (they are read once per process): factors SPD matrices of assorted sizes -- single
 and as lock-step batches through the tuning objective -- and compares with LAPACK / one-at-a-time
-fits.  Prints OK on success."""
+fits.  Then the factor bit for bit: a second set of matrices, built by + - * / only so that their bytes do not depend
+on the host's libm or BLAS, is factored and the SHA-256 of np.tril(L) compared with tests/golden/chol_factor_digests.npz,
+keyed by (variant name, n) -- every sum on this path runs in a fixed order, so a schedule returns the same bits on
+every run and a library that returns other bits has changed what it computes.  Prints OK on success.
+
+    chol_paths_check.py [VARIANT]                 all checks; the digests of VARIANT (a name of test_gpu_chol_paths.VARIANTS)
+    chol_paths_check.py --record FILE [VARIANT]   only factors the second set and writes its digests into FILE (created
+                                                  or updated).  Record every variant twice into the same file: a pair
+                                                  whose second digest differs from its first is stored empty -- it did
+                                                  not reproduce and is not checked; such pairs are findings to report.
+"""
+import hashlib
 import os
 import sys
 
@@ -18,9 +29,55 @@ def relerr(a, b):
   return float(np.max(np.abs(a - b)) / np.max(np.abs(b)))
 
 
+SIZES = (513, 1024, 1100, 1536, 1601, 2048, 2500, 3100)
+DIGESTS = os.path.join(ROOT, 'tests', 'golden', 'chol_factor_digests.npz')
+
+
+def arith_matrix(n):
+  """ SPD (a Cauchy kernel on n points of [0, 1] plus 0.05 I) from RandomState(n).rand(n) by + - * / only. """
+  x = np.random.RandomState(n).rand(n)
+  D = x[:, None] - x[None, :]
+  return 1 / (1 + 25 * D * D) + 0.05 * np.eye(n)
+
+
+def sha(a):
+  return hashlib.sha256(np.ascontiguousarray(a, dtype='<f8').tobytes()).hexdigest()
+
+
+def load_digests(path):
+  if not os.path.exists(path):
+    return {}
+  with np.load(path) as z:
+    return dict(zip((str(k) for k in z['keys']), (str(d) for d in z['digests'])))
+
+
+def factor_digests(variant, record_to=None):
+  """ Digest of M itself under 'input|n' (a differing input is not to be taken for a differing library), of
+      np.tril(L) under 'variant|n'. """
+  known = load_digests(record_to or DIGESTS)
+  for n in SIZES:
+    M = arith_matrix(n)
+    L = G.stable_cholesky(M)
+    for key, got in (('input|%d' % n, sha(M)), ('%s|%d' % (variant, n), sha(np.tril(L)))):
+      print('%s %s' % (key, got))
+      if record_to:
+        known[key] = got if known.get(key, got) == got else ''
+      elif known.get(key):        # (an empty digest: the pair did not reproduce when the file was recorded)
+        assert known[key] == got, 'the bits of %s differ from tests/golden/chol_factor_digests.npz: %s, recorded %s' % (key, got, known[key])
+      else:
+        assert key in known, '%s is not in tests/golden/chol_factor_digests.npz' % key
+  if record_to:
+    keys = sorted(known)
+    np.savez_compressed(record_to, keys=np.array(keys), digests=np.array([known[k] for k in keys]))
+
+
 def main():
   eng = get_engine()
-  for n in (513, 1024, 1100, 1536, 1601, 2048, 2500, 3100):
+  if len(sys.argv) > 1 and sys.argv[1] == '--record':
+    factor_digests(sys.argv[3] if len(sys.argv) > 3 else 'defaults', record_to=sys.argv[2])
+    print('OK')
+    return
+  for n in SIZES:
     rs = np.random.RandomState(n)
     X = rs.rand(n, 4)
     M = O.se_kernel(X, X, 1.0, np.full(4, 0.4)) + 0.05 * np.eye(n)
@@ -61,6 +118,7 @@ def main():
       one = eng.gp_fit(specs[c], X, Y - means[c], noises[c])
       assert abs(lml[c] - one.lml) <= 1e-11 * abs(one.lml), (n, c, lml[c], one.lml)
       one.free()
+  factor_digests(sys.argv[1] if len(sys.argv) > 1 else 'defaults')
   print('OK')
 
 

@@ -3,7 +3,8 @@
 look-ahead (DFH_CHOL_LR) -- are chosen by problem size and batch size; here each is forced on (and off)
 for small sizes too, in a subprocess (the switches are read once per process), so that every path sees
 ragged sizes, odd and even panel counts and lock-step batches.  The hand-off time-out and its fallback
-without hand-offs (DFH_CHOL_SAFE) are forced the same way."""
+without hand-offs (DFH_CHOL_SAFE) are forced the same way.  Each variant's factors are also held, bit for bit, to the
+digests recorded in tests/golden/chol_factor_digests.npz (tests/chol_paths_check.py)."""
 import os
 import subprocess
 import sys
@@ -44,6 +45,6 @@ VARIANTS = {
 def test_schedule_variant(engine, name):
   env = dict(os.environ)
   env.update(VARIANTS[name])
-  res = subprocess.run([sys.executable, os.path.join(HERE, 'chol_paths_check.py')], env=env, capture_output=True,
+  res = subprocess.run([sys.executable, os.path.join(HERE, 'chol_paths_check.py'), name], env=env, capture_output=True,
                        text=True, timeout=600)
   assert res.returncode == 0 and res.stdout.strip().endswith('OK'), (res.stdout[-2000:], res.stderr[-4000:])

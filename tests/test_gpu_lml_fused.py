@@ -1,4 +1,4 @@
-"""MI355X: a handful of mid-sized candidates in ONE launch (csrc/chol.hip: lml_wgf_kernel, 64 <= n <= 128 by default, at most 16
+"""MI355X: a handful of mid-sized candidates in ONE launch (csrc/lml_wg.h: lml_wgf_kernel, 64 <= n <= 128 by default, at most 16
 candidates per call -- the slice sampler's and the tree search's calls of GPFitter._tuning_objective,
 dragonfly/gp/gp_core.py:551-574 -> build_posterior :155-163 -> :222-227): the workgroup builds its candidate's Gram
 matrix itself (get_scaled_repr kernel.py:179-181, dist_squared general_utils.py:58-70, SE / Matern / additive /

@@ -1,4 +1,4 @@
-"""MI355X: the tuning objective with one workgroup per candidate (csrc/chol.hip: lml_wg_kernel, 128 < n <= 2047;
+"""MI355X: the tuning objective with one workgroup per candidate (csrc/lml_wg.h: lml_wg_kernel, 128 < n <= 2047;
 GPFitter._tuning_objective, dragonfly/gp/gp_core.py:551-574 -> build_posterior :155-163 -> :222-227): sizes around
 the 64-row tile edges (the augmented row n falls into a tile of its own when n is a multiple of 64), more
 candidates than one launch holds, candidates that need the stable_cholesky ladder inside a large group, kernels

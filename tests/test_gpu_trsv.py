@@ -1,4 +1,4 @@
-"""MI355X: the two substitutions on their own kernels (csrc/chol.hip: k_trsv_blk_fwd / k_trsv_upd_fwd / k_trsv_blk_bwd /
+"""MI355X: the two substitutions on their own kernels (csrc/trsolve.hip: k_trsv_blk_fwd / k_trsv_upd_fwd / k_trsv_blk_bwd /
 k_trsv_upd_bwd, round 6; solve_lower_triangular / solve_upper_triangular of dragonfly/utils/general_utils.py:208-221 as
 GP.build_posterior uses them, gp_core.py:161-163) against scipy.linalg.solve_triangular: sizes around the 512-block edges
 and the kernels' own edges (a last block of 1 .. 511 rows, panels shorter than the 2048 rows from which the forward update

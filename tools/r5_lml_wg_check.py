@@ -1,4 +1,4 @@
-"""Round 5: the one-workgroup-per-candidate tuning objective (chol.hip: lml_wg_kernel) against the NumPy oracle at
+"""Round 5: the one-workgroup-per-candidate tuning objective (lml_wg.h: lml_wg_kernel) against the NumPy oracle at
 sizes around its tile edges, a candidate that needs the jitter ladder, then timings of large batches.
     python tools/r5_lml_wg_check.py [quick]"""
 import os, sys, time
