@@ -104,6 +104,8 @@ SIGNATURES = {
                                   c_double_p, c_int64_p]),
   'dfh_gp_ts': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_double,
                           C.c_void_p, C.c_void_p, c_double_p, c_int64_p, c_int32_p]),
+  'dfh_gp_draw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
   'dfh_gp_add_ucb_group': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
                                      C.c_void_p, c_double_p, c_int64_p]),
   'dfh_mo_ucb_argmax': (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
@@ -142,6 +144,12 @@ SIGNATURES = {
                             C.c_double, c_double_p, c_int64_p, c_double_p, c_int64_p]),
   'dfh_mgpu_acq_argmax': (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.POINTER(C.c_void_p), c_int64_p,
                                     C.c_double, c_double_p, c_int64_p, c_double_p, c_int64_p]),
+  'dfh_mgpu_ts_halluc': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_int64_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int64,
+                                   C.POINTER(C.c_void_p), C.c_double, C.POINTER(C.c_void_p), c_double_p, c_int64_p,
+                                   c_double_p, c_int64_p, C.c_void_p]),
+  'dfh_mgpu_acq_argmax_halluc': (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.POINTER(C.c_void_p), c_int64_p,
+                                           C.POINTER(C.c_void_p), C.c_int64, C.c_double, C.POINTER(C.c_void_p),
+                                           c_double_p, c_int64_p, c_double_p, c_int64_p]),
   'dfh_mgpu_allgather_argmax': (C.c_int, [C.c_void_p, c_double_p, c_int64_p, c_double_p, c_int64_p]),
   'dfh_ctx_timings': (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
   'dfh_ctx_counters': (C.c_int, [C.c_void_p, c_int64_p]),

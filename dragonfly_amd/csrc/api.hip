@@ -171,6 +171,96 @@ int argmax_update(dfh_ctx* ctx, const double* v, int64_t m, int64_t idx_base, bo
   return DFH_OK;
 }
 
+// arg-max of every row of v [rows x ld] (np.argmax rule, index local to the row): one workgroup per row
+__global__ void k_argmax_rows(const double* __restrict__ v, long ld, long m, double* __restrict__ out_v,
+                              long* __restrict__ out_i) {
+  __shared__ double sv[256];
+  __shared__ long si[256];
+  const double* r = v + (long)blockIdx.x * ld;
+  double bv = -INFINITY;
+  long bi = LONG_MAX;
+  for (long i = threadIdx.x; i < m; i += blockDim.x) {
+    const double x = r[i];
+    if (bi == LONG_MAX || better(x, i, bv, bi)) { bv = x; bi = i; }
+  }
+  sv[threadIdx.x] = bv; si[threadIdx.x] = bi;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      const double ov = sv[threadIdx.x + s]; const long oi = si[threadIdx.x + s];
+      if (oi != LONG_MAX && (si[threadIdx.x] == LONG_MAX || better(ov, oi, sv[threadIdx.x], si[threadIdx.x]))) {
+        sv[threadIdx.x] = ov; si[threadIdx.x] = oi;
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out_v[blockIdx.x] = sv[0]; out_i[blockIdx.x] = si[0]; }
+}
+
+// S joint draws of one Thompson block in one launch: out[s][i] = mu[i] + sum_{j <= i} L[i][j] Ut[s][j], L the B x B lower
+// factor (row-major; its strict upper triangle holds stale covariance and is never read), Ut the block's normals
+// sample-major (row s at s * ldu).  One 256-thread workgroup per (tile of DRAW_TILE draws, row of L): the row is read
+// once per tile, each element multiplied into the tile's DRAW_TILE accumulator pairs, and the tiles of a row are
+// neighbours in the grid, so all but the first find the row in L2.  Per draw the arithmetic is k_gemv_rows' with
+// tri_lower (runtime.hip) operation for operation -- the thread's strided fma chain (even / odd elements apart when
+// `vec`, the condition under which that kernel takes its double2 path), the wave's shuffle tree, the four wave sums as
+// (w0 + w1) + (w2 + w3), then + mu -- so draw s is bit for bit the single draw with column s of the normals.
+#define DRAW_TILE 8
+__global__ __launch_bounds__(256) void k_tri_draw(const double* __restrict__ L, long B, const double* __restrict__ Ut,
+                                                  long ldu, int S, const double* __restrict__ mu,
+                                                  double* __restrict__ out, long ldo, int vec) {
+  __shared__ double sm[DRAW_TILE][4];
+  const long row = blockIdx.y;
+  const int s_lo = (int)blockIdx.x * DRAW_TILE;
+  const int nt = S - s_lo < DRAW_TILE ? S - s_lo : DRAW_TILE;
+  const double* a = L + row * B;
+  const long n = row + 1;                                   // only columns j <= row
+  const double* x[DRAW_TILE];                               // a short tile repeats its last draw: no branch in the loop
+#pragma unroll
+  for (int t = 0; t < DRAW_TILE; ++t) x[t] = Ut + (long)(s_lo + (t < nt ? t : nt - 1)) * ldu;
+  double s0[DRAW_TILE], s1[DRAW_TILE];
+#pragma unroll
+  for (int t = 0; t < DRAW_TILE; ++t) { s0[t] = 0.0; s1[t] = 0.0; }
+  if (vec) {
+    const bool x2 = ((reinterpret_cast<uintptr_t>(Ut) & 15) == 0) && ((ldu & 1) == 0);
+    const long n2 = n >> 1;
+    for (long j = threadIdx.x; j < n2; j += 256) {
+      const double2_t av = reinterpret_cast<const double2_t*>(a)[j];
+#pragma unroll
+      for (int t = 0; t < DRAW_TILE; ++t) {
+        double2_t xv;
+        if (x2) xv = reinterpret_cast<const double2_t*>(x[t])[j];
+        else { xv.x = x[t][2 * j]; xv.y = x[t][2 * j + 1]; }
+        s0[t] = fma(av.x, xv.x, s0[t]);
+        s1[t] = fma(av.y, xv.y, s1[t]);
+      }
+    }
+    if ((n & 1) && threadIdx.x == 0) {
+      const double al = a[n - 1];
+#pragma unroll
+      for (int t = 0; t < DRAW_TILE; ++t) s0[t] = fma(al, x[t][n - 1], s0[t]);
+    }
+  } else {
+    for (long j = threadIdx.x; j < n; j += 256) {
+      const double aj = a[j];
+#pragma unroll
+      for (int t = 0; t < DRAW_TILE; ++t) s0[t] = fma(aj, x[t][j], s0[t]);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < DRAW_TILE; ++t) {
+    double s = s0[t] + s1[t];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) sm[t][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nt) {
+    const int t = threadIdx.x;
+    const double v = (sm[t][0] + sm[t][1]) + (sm[t][2] + sm[t][3]);
+    out[(long)(s_lo + t) * ldo + row] = v + mu[row];
+  }
+}
+
 // Phi(x): scipy.special.ndtr structure (xsf/cephes/ndtr.h) on the device erf/erfc
 __device__ __forceinline__ double ndtr_dev(double a) {
   if (a != a) return a;
@@ -1312,9 +1402,12 @@ extern "C" int dfh_gp_predict_covar(dfh_gp* gp, const double* Xs, int64_t m, con
 // `h` (halluc_prepare's block form of the q in-progress points, gp_core.py:192-220), lose the rank-q term V2^T V2 as well.
 // samples_dev (optional, device [m]) receives the draw without a trip to the host; the arg-max is skipped when neither
 // best_val nor best_idx is wanted (the multi-objective call scalarises K draws first).
+// S > 1 (dfh_gp_draw): U is [m x S] row-major, np.random.normal(size=(m, S)), and every block's factor serves all S draws
+// in one launch of k_tri_draw; samples_dev / samples_out are then [S x m] and best_val / best_idx [S].  S == 1 runs the
+// code, kernels and synchronisation points it always ran.
 static int ts_run(dfh_gp* gp, dfh_gp* cov_gp, const Halluc* h, const double* Xs, int64_t m, int64_t block, const double* U,
                   double mean_const, const double* mean_vals, double* samples_dev, double* samples_out, double* best_val,
-                  int64_t* best_idx, int32_t* jitter_powers_out) {
+                  int64_t* best_idx, int32_t* jitter_powers_out, int32_t S = 1) {
   dfh_ctx* ctx = gp->ctx;
   DFH_HIP(hipSetDevice(ctx->device));
   const KernDev& kd = cov_gp->kd;
@@ -1336,6 +1429,20 @@ static int ts_run(dfh_gp* gp, dfh_gp* cov_gp, const Halluc* h, const double* Xs,
   const int64_t lb_slots = std::max<int64_t>(1, std::min<int64_t>(ts_batch, mc_max / block));
   double* Lb = nullptr;
   DFH_TRY(scratch_get(ctx, SCR_TSL, (size_t)lb_slots * block * block * 8, (void**)&Lb));
+  // S > 1: the chunk's normals sample-major (even leading dimension: a block's offset alone decides the 16-byte
+  // alignment, as it does for the single draw's vector) | its S draws, rows tight | the per-draw winners
+  DevBlock multi(ctx);
+  const int64_t ldu = (mc_max + 1) & ~(int64_t)1;
+  double* Ut = nullptr; double* sampS = nullptr; double* win_v = nullptr; long* win_i = nullptr;
+  std::vector<double> hv, bvS; std::vector<long> hi; std::vector<int64_t> biS; std::vector<char> haveS;
+  if (S > 1) {
+    DFH_TRY(dev_alloc(ctx, ((size_t)S * ldu + (size_t)S * mc_max + 2 * (size_t)S) * 8, &multi.p));
+    Ut = static_cast<double*>(multi.p);
+    sampS = Ut + (int64_t)S * ldu;
+    win_v = sampS + (int64_t)S * mc_max;
+    win_i = reinterpret_cast<long*>(win_v + S);
+    hv.resize(S); hi.resize(S); haveS.assign(S, 0); bvS.assign(S, 0.0); biS.assign(S, -1);
+  }
   // Two-stage software pipeline over chunks.  Stage 1 (low-priority `bulk` stream): cross kernel
   // matrix, mu, and the posterior TRSM of chunk c+1 -- large MFMA GEMMs.  Stage 2 (main + panel
   // streams): per TS block of chunk c the covariance SYRK, its stable_cholesky (latency-bound
@@ -1387,8 +1494,9 @@ static int ts_run(dfh_gp* gp, dfh_gp* cov_gp, const Halluc* h, const double* Xs,
     if (c + 1 < nchunks) DFH_TRY(stage1(c + 1));        // enqueue ahead: overlaps with the blocks below
     DFH_HIP(hipStreamWaitEvent(mainS, ev_ready[p], 0));
     const double* u_c = nullptr;
-    if (u_dev) u_c = U + i0;
-    else DFH_TRY(to_device(ctx, U + i0, (size_t)mc * 8, SCR_STAGE_C, &u_c));
+    if (u_dev) u_c = U + i0 * S;
+    else DFH_TRY(to_device(ctx, U + i0 * S, (size_t)mc * S * 8, SCR_STAGE_C, &u_c));
+    if (S > 1) DFH_TRY(transpose_matrix(ctx, u_c, S, Ut, ldu, mc, S));
     const double* mv_c = nullptr;
     if (mean_vals) {
       if (mv_dev) mv_c = mean_vals + i0;
@@ -1421,6 +1529,18 @@ static int ts_run(dfh_gp* gp, dfh_gp* cov_gp, const Halluc* h, const double* Xs,
       int32_t jp = INT32_MIN;
       DFH_TRY(stable_cholesky_device(ctx, dst, B, nullptr, true, build_sigma, &jp, nullptr));
       if (jitter_powers_out) jitter_powers_out[bidx] = jp;
+      return DFH_OK;
+    };
+    // s = L u + mu of one factored block: the single draw's kernel, or all S draws in one launch.  `vec` is the single
+    // draw's choice of summation order for this block (gemv_rows: even leading dimension, factor and normals 16-byte
+    // aligned -- the caller's U taken to be aligned as a whole), so that draw s is that call's with column s.
+    auto draw_block = [&](const double* Lf, int64_t b0, int64_t B) -> int {
+      if (S == 1) return gemv_rows(ctx, Lf, B, B, B, u_c + b0, 1.0, mu_raw + b0, 1.0, samp + b0, true);
+      const int vec = ((B & 1) == 0) && ((reinterpret_cast<uintptr_t>(Lf) & 15) == 0) && ((((u_dev ? i0 : 0) + b0) & 1) == 0);
+      hipLaunchKernelGGL(k_tri_draw, dim3((unsigned)((S + DRAW_TILE - 1) / DRAW_TILE), (unsigned)B), dim3(256), 0, ctx->stream,
+                         Lf, (long)B, (const double*)(Ut + b0), (long)ldu, (int)S, (const double*)(mu_raw + b0), sampS + b0,
+                         (long)mc, vec);
+      DFH_LAUNCH_CHECK();
       return DFH_OK;
     };
     const int64_t nfull = mc / block;
@@ -1460,23 +1580,54 @@ static int ts_run(dfh_gp* gp, dfh_gp* cov_gp, const Halluc* h, const double* Xs,
       }
       for (int b = 0; b < nb; ++b) {
         const int64_t b0 = (g0 + b) * B;
-        DFH_TRY(gemv_rows(ctx, Lb + b * B * B, B, B, B, u_c + b0, 1.0, mu_raw + b0, 1.0, samp + b0, true));
+        DFH_TRY(draw_block(Lb + b * B * B, b0, B));
       }
     }
     if (nfull * block < mc) {           // ragged last block
       const int64_t b0 = nfull * block, B = mc - b0;
       SectionTimer t(ctx, DFH_T_TS);
       DFH_TRY(single_block(b0, B, Lb, blk_idx + nfull));
-      DFH_TRY(gemv_rows(ctx, Lb, B, B, B, u_c + b0, 1.0, mu_raw + b0, 1.0, samp + b0, true));
+      DFH_TRY(draw_block(Lb, b0, B));
     }
     blk_idx += (mc + block - 1) / block;
-    if (best_val || best_idx) DFH_TRY(argmax_update(ctx, samp, mc, i0, &have, &bv, &bi));
-    if (samples_dev) DFH_HIP(hipMemcpyAsync(samples_dev + i0, samp, (size_t)mc * 8, hipMemcpyDeviceToDevice, mainS));
-    if (samples_out) DFH_TRY(from_device(ctx, samples_out + i0, samp, (size_t)mc * 8));
+    if (S > 1) {
+      if (best_val || best_idx) {
+        hipLaunchKernelGGL(k_argmax_rows, dim3((unsigned)S), dim3(256), 0, mainS, (const double*)sampS, (long)mc, (long)mc,
+                           win_v, win_i);
+        DFH_LAUNCH_CHECK();
+        DFH_HIP(hipMemcpyAsync(hv.data(), win_v, (size_t)S * 8, hipMemcpyDeviceToHost, mainS));
+        DFH_HIP(hipMemcpyAsync(hi.data(), win_i, (size_t)S * 8, hipMemcpyDeviceToHost, mainS));
+        DFH_HIP(hipStreamSynchronize(mainS));
+        for (int32_t si = 0; si < S; ++si) {
+          const int64_t gi = i0 + (int64_t)hi[si];
+          if (!haveS[si] || host_better(hv[si], gi, bvS[si], biS[si])) { bvS[si] = hv[si]; biS[si] = gi; haveS[si] = 1; }
+        }
+      }
+      if (samples_dev)
+        DFH_HIP(hipMemcpy2DAsync(samples_dev + i0, (size_t)m * 8, sampS, (size_t)mc * 8, (size_t)mc * 8, (size_t)S,
+                                 hipMemcpyDeviceToDevice, mainS));
+      if (samples_out) {
+        const bool out_dev = is_device_ptr(samples_out);
+        DFH_HIP(hipMemcpy2DAsync(samples_out + i0, (size_t)m * 8, sampS, (size_t)mc * 8, (size_t)mc * 8, (size_t)S,
+                                 out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, mainS));
+        if (!out_dev) DFH_HIP(hipStreamSynchronize(mainS));
+      }
+    } else {
+      if (best_val || best_idx) DFH_TRY(argmax_update(ctx, samp, mc, i0, &have, &bv, &bi));
+      if (samples_dev) DFH_HIP(hipMemcpyAsync(samples_dev + i0, samp, (size_t)mc * 8, hipMemcpyDeviceToDevice, mainS));
+      if (samples_out) DFH_TRY(from_device(ctx, samples_out + i0, samp, (size_t)mc * 8));
+    }
     DFH_HIP(hipEventRecord(ev_free[p], mainS));
   }
   DFH_HIP(hipStreamSynchronize(mainS));
   DFH_HIP(hipStreamSynchronize(bulkS));
+  if (S > 1) {
+    for (int32_t si = 0; si < S; ++si) {
+      if (best_val) best_val[si] = bvS[si];
+      if (best_idx) best_idx[si] = biS[si];
+    }
+    return DFH_OK;
+  }
   if (best_val) *best_val = bv;
   if (best_idx) *best_idx = bi;
   return DFH_OK;
@@ -1493,6 +1644,33 @@ extern "C" int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
   if (best_val) *best_val = bv;
   if (best_idx) *best_idx = bi;
   return DFH_OK;
+}
+
+// The joint draw of one GP with points in progress and S samples (include/dfhip.h): gp.draw_samples(S, Xs) and
+// gp.draw_samples_with_hallucinated_observations(S, Xs, Xh) (gp_core.py:250-261) block by block.  One covariance and one
+// stable_cholesky per block, shared by the S draws.
+extern "C" int dfh_gp_draw(dfh_gp* gp, const double* Xs, int64_t m, int64_t block, const double* Xh, int64_t q,
+                           const double* U, int32_t S, double mean_const, const double* mean_vals, double* samples_out,
+                           double* best_vals, int64_t* best_idx, int32_t* jitter_powers_out) {
+  DFH_ARG(gp && Xs && U && m >= 1 && block >= 1);
+  DFH_ARG(S >= 1 && q >= 0 && (q == 0 || Xh));
+  DFH_ARG(!gp->gram);      // needs the kernel: this posterior was built from a Gram matrix
+  DFH_HIP(hipSetDevice(gp->ctx->device));
+  // the augmentation as dfh_mo_ts_argmax takes it: block form, or the augmented GP factored from scratch with the ladder
+  Halluc h;
+  dfh_gp* aug = nullptr;
+  if (q > 0) {
+    int rc = halluc_prepare(gp, Xh, q, &h);
+    if (rc == DFH_ERR_NOT_PD) {
+      h.q = 0;
+      rc = halluc_augmented_gp(gp, Xh, q, &aug);
+    }
+    DFH_TRY(rc);
+  }
+  const int rc = ts_run(gp, aug ? aug : gp, q > 0 ? &h : nullptr, Xs, m, block, U, mean_const, mean_vals, nullptr, samples_out,
+                        best_vals, best_idx, jitter_powers_out, S);
+  if (aug) dfh_gp_free(aug);
+  return rc;
 }
 
 // ---- multi-objective acquisitions: K fitted GPs, one call -------------------------------------------------------

@@ -585,6 +585,66 @@ extern "C" int dfh_mgpu_acq_argmax(dfh_mgpu* mg, int acq, const double* params, 
   return exchange(mg, vals, idxs, best_val, best_idx);
 }
 
+// dfh_mgpu_ts / dfh_mgpu_acq_argmax with evaluations in progress: rank r's copy Xh[r] of the q points (each rank runs
+// the block form of the augmentation, or its fall-back, on its own replica), an optional per-rank prior mean over the
+// shard, and -- Thompson -- every rank's per-block jitter powers, rank after rank.  The winner is the single-device
+// call's (dfh_gp_draw with S = 1, dfh_gp_acq_argmax with Xh) on the concatenated candidates.
+extern "C" int dfh_mgpu_ts_halluc(dfh_mgpu* mg, const double* const* Xs, const int64_t* m, int64_t block,
+                                  const double* const* Xh, int64_t q, const double* const* U, double mean_const,
+                                  const double* const* mean_vals, double* best_val, int64_t* best_idx,
+                                  double* local_vals, int64_t* local_idx, int32_t* jitter_powers_out) {
+  DFH_ARG(mg && Xs && m && U && block >= 1 && q >= 0 && (q == 0 || Xh));
+  std::vector<int64_t> off((size_t)mg->n + 1, 0), boff((size_t)mg->n + 1, 0);
+  for (int r = 0; r < mg->n; ++r) {
+    DFH_ARG(m[r] >= 0 && (m[r] == 0 || (Xs[r] && U[r] && (q == 0 || Xh[r]))) && mg->gps[r]);
+    off[r + 1] = off[r] + m[r];
+    boff[r + 1] = boff[r] + (m[r] + block - 1) / block;
+  }
+  std::vector<double> vals((size_t)mg->n, NAN);
+  std::vector<int64_t> idxs((size_t)mg->n, -1);
+  DFH_TRY(fan_out(mg, [&](int r) -> int {
+    if (m[r] == 0) return DFH_OK;
+    double v = NAN; int64_t i = -1;
+    DFH_TRY(dfh_gp_draw(mg->gps[r], Xs[r], m[r], block, q > 0 ? Xh[r] : nullptr, q, U[r], 1, mean_const,
+                        mean_vals ? mean_vals[r] : nullptr, nullptr, &v, &i,
+                        jitter_powers_out ? jitter_powers_out + boff[r] : nullptr));
+    vals[r] = v; idxs[r] = off[r] + i;
+    return DFH_OK;
+  }));
+  for (int r = 0; r < mg->n; ++r) {
+    if (local_vals) local_vals[r] = vals[r];
+    if (local_idx) local_idx[r] = idxs[r];
+  }
+  return exchange(mg, vals, idxs, best_val, best_idx);
+}
+
+extern "C" int dfh_mgpu_acq_argmax_halluc(dfh_mgpu* mg, int acq, const double* params, const double* const* Xs,
+                                          const int64_t* m, const double* const* Xh, int64_t q, double mean_const,
+                                          const double* const* mean_vals, double* best_val, int64_t* best_idx,
+                                          double* local_vals, int64_t* local_idx) {
+  DFH_ARG(mg && Xs && m && q >= 0 && (q == 0 || Xh));
+  std::vector<int64_t> off((size_t)mg->n + 1, 0);
+  for (int r = 0; r < mg->n; ++r) {
+    DFH_ARG(m[r] >= 0 && (m[r] == 0 || (Xs[r] && (q == 0 || Xh[r]))) && mg->gps[r]);
+    off[r + 1] = off[r] + m[r];
+  }
+  std::vector<double> vals((size_t)mg->n, NAN);
+  std::vector<int64_t> idxs((size_t)mg->n, -1);
+  DFH_TRY(fan_out(mg, [&](int r) -> int {
+    if (m[r] == 0) return DFH_OK;
+    double v = NAN; int64_t i = -1;
+    DFH_TRY(dfh_gp_acq_argmax(mg->gps[r], acq, params, Xs[r], m[r], q > 0 ? Xh[r] : nullptr, q, mean_const,
+                              mean_vals ? mean_vals[r] : nullptr, nullptr, &v, &i));
+    vals[r] = v; idxs[r] = off[r] + i;
+    return DFH_OK;
+  }));
+  for (int r = 0; r < mg->n; ++r) {
+    if (local_vals) local_vals[r] = vals[r];
+    if (local_idx) local_idx[r] = idxs[r];
+  }
+  return exchange(mg, vals, idxs, best_val, best_idx);
+}
+
 // The exchange on its own: per-rank (value, global index) pairs in, the reduced pair out.
 extern "C" int dfh_mgpu_allgather_argmax(dfh_mgpu* mg, const double* vals, const int64_t* idxs, double* best_val,
                                          int64_t* best_idx) {

@@ -622,6 +622,10 @@ class Engine(object):
 class FittedGP(object):
   """ Handle of a dfh_gp: K, L, alpha live on the device. """
 
+  # Capability: joint draws with points in progress and several samples run as one device call (draw, and
+  # thompson's X_halluc).  Callers choose the fused route by this attribute, never by the handle's type.
+  fused_draws = True
+
   def __init__(self, engine, spec, X, y_centred, noise_var, allow_jitter=True, handle_non_psd_kernels='guaranteed_psd'):
     self.engine = engine
     self.handle = None
@@ -791,9 +795,39 @@ class FittedGP(object):
       return bv.value, bi.value, vals
     return bv.value, bi.value
 
-  def thompson(self, Xs, U, block=4096, mean_const=0.0, mean_vals=None, return_samples=False):
+  def draw(self, Xs, U, num_samples=1, block=None, X_halluc=None, mean_const=0.0, mean_vals=None,
+           return_samples=True):
+    """ num_samples joint draws over the candidates Xs in one device call (dfh_gp_draw): with block None (one
+        block) gp.draw_samples(num_samples, Xs), and with X_halluc
+        gp.draw_samples_with_hallucinated_observations(num_samples, Xs, X_halluc).  U: the standard normals
+        np.random.normal(size=(m, num_samples)), host array or DeviceArray.  Returns (samples [S x m] or
+        None, best_vals [S], best_idx [S], jitter_powers [blocks]). """
+    Xs, m = self._rows(Xs)
+    S = int(num_samples)
+    Uh = U if isinstance(U, DeviceArray) else _f64(np.ravel(U))
+    if Uh.size != m * S:
+      raise ValueError('U must hold one standard normal per candidate and sample.')
+    block = m if block is None else int(min(block, m))
+    nblk = (m + block - 1) // block
+    Xh, q = (None, 0) if X_halluc is None or len(X_halluc) == 0 else self._rows(X_halluc)
+    samples = np.empty((S, m)) if return_samples else None
+    bvs = np.empty(max(S, 1), dtype=np.float64)
+    bis = np.empty(max(S, 1), dtype=np.int64)
+    jps = (C.c_int32 * nblk)()
+    mv = None if mean_vals is None else (mean_vals if isinstance(mean_vals, DeviceArray)
+                                         else _f64(mean_vals))
+    check(self.engine.lib.dfh_gp_draw(self.handle, _ptr(Xs), m, block, _ptr(Xh), q, _ptr(Uh), S, float(mean_const),
+                                      _ptr(mv), _ptr(samples), _ptr(bvs), _ptr(bis), jps))
+    return samples, bvs, bis, [None if j == INT32_MIN else j for j in jps]
+
+  def thompson(self, Xs, U, block=4096, mean_const=0.0, mean_vals=None, return_samples=False, X_halluc=None):
     """ Blocked-joint Thompson sample over the candidates. Returns (best_val, best_idx[, samples,
-        jitter_powers]). """
+        jitter_powers]).  X_halluc: the points in progress, hallucinated into the covariance (dfh_gp_draw). """
+    if X_halluc is not None and len(X_halluc) > 0:
+      samples, bvs, bis, powers = self.draw(Xs, U, 1, block, X_halluc, mean_const, mean_vals, return_samples)
+      if return_samples:
+        return float(bvs[0]), int(bis[0]), samples[0], powers
+      return float(bvs[0]), int(bis[0])
     Xs, m = self._rows(Xs)
     Uh = U if isinstance(U, DeviceArray) else _f64(np.ravel(U))
     block = int(min(block, m))

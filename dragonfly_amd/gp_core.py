@@ -320,7 +320,10 @@ class GP(object):
     """ gp_core.py:250-254.  A single joint draw at X_test runs fused on the device
         (covariance, stable_cholesky and L u never leave HBM); the standard normals continue
         the global np.random state exactly as draw_gaussian_samples' np.random.normal call does
-        (Engine.random_normals: generated on the device, bit for bit). """
+        (Engine.random_normals: generated on the device, bit for bit).  So do several draws where
+        the fitted handle can (FittedGP.fused_draws): one factorisation serves them all. """
+    if num_samples > 1 and self._can_fuse_draws(num_samples, X_test):
+      return self._fused_draws(num_samples, X_test, None)
     if X_test is not None and num_samples == 1 and self.num_tr_data > 0 and not self._generic:
       Xt = self._points_array(X_test)
       test_mean = self.mean_func(X_test)
@@ -336,8 +339,33 @@ class GP(object):
       mean_vals, covar = self.eval(X_test, 'covar')
     return draw_gaussian_samples(num_samples, mean_vals, covar)
 
+  def _can_fuse_draws(self, num_samples, X_test):
+    """ Joint draws in one device call: a device kernel, data, and a fitted handle that says it can (the
+        stand-in engines of the CPU tests do not, and keep the host route). """
+    return X_test is not None and num_samples >= 1 and self.num_tr_data > 0 and not self._generic and \
+           getattr(self._need_fit(), 'fused_draws', False)
+
+  def _fused_draws(self, num_samples, X_test, X_halluc):
+    """ num_samples joint draws at X_test, with the points in progress X_halluc (or None) hallucinated:
+        covariance, stable_cholesky and L U never leave HBM.  The normals are draw_gaussian_samples'
+        np.random.normal(size=(m, num_samples)) (general_utils.py:230), generated on the device when
+        DEVICE_NORMALS is on; either way the global state ends where the reference leaves it. """
+    Xt = self._points_array(X_test)
+    Xh = None if X_halluc is None else self._points_array(X_halluc)
+    test_mean = self.mean_func(X_test)
+    fit = self._need_fit()
+    draw = getattr(fit.engine, 'random_normals', None)
+    on_device = draw is not None and DEVICE_NORMALS
+    U = draw(len(Xt) * num_samples) if on_device else np.random.normal(size=(len(Xt), num_samples))
+    samples = fit.draw(Xt, U, num_samples=num_samples, X_halluc=Xh, mean_vals=test_mean)[0]
+    if on_device:
+      U.free()
+    return samples
+
   def draw_samples_with_hallucinated_observations(self, num_samples, X_test, X_halluc):
-    """ gp_core.py:256-261 """
+    """ gp_core.py:256-261 -- fused on the device like draw_samples where the fitted handle can. """
+    if self._can_fuse_draws(num_samples, X_test) and len(X_halluc) > 0:
+      return self._fused_draws(num_samples, X_test, X_halluc)
     mean_vals, aug_covar = self.eval_with_hallucinated_observations(X_test, X_halluc,
                                                                     uncert_form='covar')
     return draw_gaussian_samples(num_samples, mean_vals, aug_covar)

@@ -243,10 +243,14 @@ def asy_ts(gp, anc_data):
     anc_data.max_evals *= 4
     anc_data.acq_opt_method = 'rand'
   Xh = _halluc_points(anc_data)
-  fused = Xh is None and anc_data.domain.get_type() == 'euclidean' and _is_device_gp(gp)
+  fused = anc_data.domain.get_type() == 'euclidean' and _is_device_gp(gp)
+  if fused and Xh is not None:
+    # with evaluations in progress: only where the fitted handle draws with them in one call (FittedGP.fused_draws)
+    fused = getattr(gp.device_gp, 'fused_draws', False)
   if not fused:
     return maximise_acquisition(get_gp_sampler_for_parallel_strategy(gp, anc_data), anc_data,
                                 vectorised=True)
+  halluc = {} if Xh is None else {'X_halluc': Xh}
   # covariance, stable_cholesky, L u and the arg-max stay on the device; the standard normals are
   # np.random.normal(size=(m, 1)) as in draw_gaussian_samples (general_utils.py:230) -- drawn in HBM
   # as well (Engine.random_normals continues the global state bit for bit): nothing of size m
@@ -254,16 +258,16 @@ def asy_ts(gp, anc_data):
   if DEVICE_CANDIDATES:
     cands, mean = _device_candidates(gp, anc_data)
     normals = gp.device_gp.engine.random_normals(cands.shape[0])
-    _, idx = gp.device_gp.thompson(cands, normals, block=cands.shape[0], **mean)
+    _, idx = gp.device_gp.thompson(cands, normals, block=cands.shape[0], **mean, **halluc)
     normals.free()
     return cands.row(idx)
   cands = _candidates(anc_data)
   normals = np.random.normal(size=(len(cands), 1)).ravel()
   if gaplog.ENABLED:
-    _, idx, samples, _ = gp.device_gp.thompson(cands, normals, block=len(cands), mean_vals=gp.mean_func(cands), return_samples=True)
+    _, idx, samples, _ = gp.device_gp.thompson(cands, normals, block=len(cands), mean_vals=gp.mean_func(cands), return_samples=True, **halluc)
     gaplog.top2('thompson', samples)
     return cands[idx]
-  _, idx = gp.device_gp.thompson(cands, normals, block=len(cands), mean_vals=gp.mean_func(cands))
+  _, idx = gp.device_gp.thompson(cands, normals, block=len(cands), mean_vals=gp.mean_func(cands), **halluc)
   return cands[idx]
 
 

@@ -403,27 +403,68 @@ class MultiEngine(object):
     sizes = np.ascontiguousarray([0 if s is None else s.shape[0] for s in out], dtype=np.int64)
     return out, sizes
 
-  def thompson(self, cand_shards, U_shards, block=4096, mean_const=0.0, return_local=False):
+  def _halluc_args(self, X_halluc, mean_vals):
+    """ What the *_halluc exports add: rank r's copy of the points in progress (a host array shared by all ranks, or one
+        host array / DeviceArray per rank) and the optional per-rank prior means over the shards. """
+    from .engine import DeviceArray, _f64      # pylint: disable=import-outside-toplevel
+    if X_halluc is None:
+      Xh, q = [None] * self.size, 0
+    else:
+      Xh = [x if isinstance(x, DeviceArray) else _f64(x) for x in self._per_rank(X_halluc)]
+      q = int(Xh[0].shape[0])
+    mv = None
+    if mean_vals is not None:
+      mv = [v if v is None or isinstance(v, DeviceArray) else _f64(np.ravel(v)) for v in self._per_rank(mean_vals)]
+    return Xh, q, mv
+
+  def thompson(self, cand_shards, U_shards, block=4096, mean_const=0.0, return_local=False, X_halluc=None,
+               mean_vals=None):
     """ Blocked-joint Thompson sampling over the concatenation of the shards (cut them with
-        shard_bounds(..., align=block)); returns (best value, GLOBAL index[, per-rank winners]). """
+        shard_bounds(..., align=block)); returns (best value, GLOBAL index[, per-rank winners]).
+        X_halluc: the points in progress, hallucinated on every rank (dfh_mgpu_ts_halluc; mean_vals: the prior mean
+        over each rank's shard); return_local then also gives each rank's per-block jitter powers. """
     Xs, ms = self._shards(cand_shards)
     Us, _ = self._shards([None if u is None else np.ravel(u) if not hasattr(u, 'ptr') else u for u in U_shards])
     bv, bi = C.c_double(0), C.c_int64(-1)
     lv = (C.c_double * self.size)()
     li = (C.c_int64 * self.size)()
+    if X_halluc is not None or mean_vals is not None:
+      Xh, q, mv = self._halluc_args(X_halluc, mean_vals)
+      nblk = [int(-(-int(m) // int(block))) for m in ms]
+      jps = (C.c_int32 * max(sum(nblk), 1))()
+      check(self.lib.dfh_mgpu_ts_halluc(self.handle, _ptr_array(Xs), ms.ctypes.data_as(_lib.c_int64_p), int(block),
+                                        _ptr_array(Xh), q, _ptr_array(Us), float(mean_const),
+                                        None if mv is None else _ptr_array(mv), C.byref(bv), C.byref(bi), lv, li, jps))
+      if return_local:
+        flat = [None if j == _lib.INT32_MIN else int(j) for j in jps]
+        starts = np.concatenate([[0], np.cumsum(nblk)])
+        powers = [flat[int(starts[r]):int(starts[r + 1])] for r in range(self.size)]
+        return float(bv.value), int(bi.value), list(zip(list(lv), list(li))), powers
+      return float(bv.value), int(bi.value)
     check(self.lib.dfh_mgpu_ts(self.handle, _ptr_array(Xs), ms.ctypes.data_as(_lib.c_int64_p), int(block),
                                _ptr_array(Us), float(mean_const), C.byref(bv), C.byref(bi), lv, li))
     if return_local:
       return float(bv.value), int(bi.value), list(zip(list(lv), list(li)))
     return float(bv.value), int(bi.value)
 
-  def acq_argmax(self, acq, cand_shards, params=(0.0, 0.0), mean_const=0.0, return_local=False):
+  def acq_argmax(self, acq, cand_shards, params=(0.0, 0.0), mean_const=0.0, return_local=False, X_halluc=None,
+                 mean_vals=None):
+    """ Fused posterior + acquisition + arg-max over the concatenation of the shards; X_halluc / mean_vals as in
+        thompson (dfh_mgpu_acq_argmax_halluc). """
     from .engine import ACQ_IDS      # pylint: disable=import-outside-toplevel
     Xs, ms = self._shards(cand_shards)
     p = (C.c_double * 2)(float(params[0]), float(params[1]) if len(params) > 1 else 0.0)
     bv, bi = C.c_double(0), C.c_int64(-1)
     lv = (C.c_double * self.size)()
     li = (C.c_int64 * self.size)()
+    if X_halluc is not None or mean_vals is not None:
+      Xh, q, mv = self._halluc_args(X_halluc, mean_vals)
+      check(self.lib.dfh_mgpu_acq_argmax_halluc(self.handle, ACQ_IDS[acq], p, _ptr_array(Xs),
+                                                ms.ctypes.data_as(_lib.c_int64_p), _ptr_array(Xh), q, float(mean_const),
+                                                None if mv is None else _ptr_array(mv), C.byref(bv), C.byref(bi), lv, li))
+      if return_local:
+        return float(bv.value), int(bi.value), list(zip(list(lv), list(li)))
+      return float(bv.value), int(bi.value)
     check(self.lib.dfh_mgpu_acq_argmax(self.handle, ACQ_IDS[acq], p, _ptr_array(Xs),
                                        ms.ctypes.data_as(_lib.c_int64_p), float(mean_const), C.byref(bv),
                                        C.byref(bi), lv, li))

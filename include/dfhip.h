@@ -317,6 +317,27 @@ int dfh_gp_ts(dfh_gp* gp, const double* Xs, int64_t m, int64_t block, const doub
               double mean_const, const double* mean_vals, double* samples_out,
               double* best_val, int64_t* best_idx, int32_t* jitter_powers_out);
 
+/* The joint draw with evaluations in progress and S samples: block by block as dfh_gp_ts, one covariance
+ * and one stable_cholesky (jitter ladder included) per block, shared by all S draws; draw s is
+ * mu + L_b U_b[:, s].  U is [m x S] row-major -- np.random.normal(size=(m, S)), what
+ * draw_gaussian_samples (utils/general_utils.py:224-232) draws.  With block >= m and q == 0 the call is
+ * gp.draw_samples(S, Xs) (gp/gp_core.py:250-254); with q > 0 it is
+ * gp.draw_samples_with_hallucinated_observations(S, Xs, Xh) (gp_core.py:256-261): the mean from the real
+ * data, the covariance from the GP augmented with Xh [q x d] (block form, or the augmented GP factored
+ * from scratch where that is not positive definite, as in dfh_mo_ts_argmax).  The product L_b U_b is one
+ * launch for all S draws, in the single draw's summation order: row s of an S-draw equals, bit for bit,
+ * the S = 1 call with column s of U (an aligned, contiguous vector), and S = 1, q = 0 is dfh_gp_ts.
+ * samples_out: optional [S x m], sample-major; best_vals / best_idx: optional [S], np.argmax's winner of
+ * each draw (first NaN, else first maximum); jitter_powers_out: optional [ceil(m/block)], INT32_MIN =
+ * none.  Xs, U and mean_vals may be host or device pointers.  DFH_ERR_BAD_ARG, before any launch, for
+ * S < 1, q < 0, q > 0 without Xh, and a posterior built from a Gram matrix.                            */
+int dfh_gp_draw(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
+                const double* Xh, int64_t q,            /* in-progress points, NULL / 0 = none */
+                const double* U, int32_t S,             /* [m x S] row-major */
+                double mean_const, const double* mean_vals /* [m] or NULL */,
+                double* samples_out /* [S x m] or NULL */, double* best_vals /* [S] or NULL */,
+                int64_t* best_idx /* [S] or NULL */, int32_t* jitter_powers_out /* [ceil(m/block)] or NULL */);
+
 /* add-UCB per-group posterior (gpb_acquisitions.py:139-189): for additive-kernel GPs,
  * group g's acquisition over its own candidate set Xg[m x |g|]:
  *   mu_g = scale*k_g(Xg, X[:,g]) alpha ; sd_g from the shared L ; val = mu_g + beta*sd_g.   */
@@ -510,6 +531,23 @@ int dfh_mgpu_ts(dfh_mgpu* mg, const double* const* Xs, const int64_t* m, int64_t
 int dfh_mgpu_acq_argmax(dfh_mgpu* mg, int acq, const double* params, const double* const* Xs,
                         const int64_t* m, double mean_const, double* best_val, int64_t* best_idx,
                         double* local_vals, int64_t* local_idx);
+/* The same two calls with evaluations in progress.  Xh[r] is rank r's copy of the q in-progress points
+ * [q x d] -- a host pointer (the same one for every rank will do) or a pointer into rank r's HBM; NULL /
+ * q == 0 = none.  Each rank builds the augmentation on its own replica (block form, or the augmented GP
+ * factored from scratch where that is not positive definite).  mean_vals: NULL, or [n_devices] pointers
+ * (entries may be NULL) to the prior mean over rank r's shard, which then replaces mean_const there.
+ * jitter_powers_out (Thompson): NULL or [sum_r ceil(m[r] / block)], rank after rank, INT32_MIN = none.
+ * The contract is the one above: the global winner is that of the single-device call -- dfh_gp_draw with
+ * S = 1, or dfh_gp_acq_argmax with Xh -- on the concatenated candidates (Thompson: shards cut on
+ * multiples of `block`).                                                                            */
+int dfh_mgpu_ts_halluc(dfh_mgpu* mg, const double* const* Xs, const int64_t* m, int64_t block,
+                       const double* const* Xh, int64_t q, const double* const* U, double mean_const,
+                       const double* const* mean_vals, double* best_val, int64_t* best_idx,
+                       double* local_vals, int64_t* local_idx, int32_t* jitter_powers_out);
+int dfh_mgpu_acq_argmax_halluc(dfh_mgpu* mg, int acq, const double* params, const double* const* Xs,
+                               const int64_t* m, const double* const* Xh, int64_t q, double mean_const,
+                               const double* const* mean_vals, double* best_val, int64_t* best_idx,
+                               double* local_vals, int64_t* local_idx);
 /* the exchange alone: vals / idxs [n_devices] in, the reduced pair out                          */
 int dfh_mgpu_allgather_argmax(dfh_mgpu* mg, const double* vals, const int64_t* idxs,
                               double* best_val, int64_t* best_idx);
