@@ -91,7 +91,7 @@ struct dfh_ctx {
   hipEvent_t tev0[DFH_T_COUNT] = {nullptr}, tev1[DFH_T_COUNT] = {nullptr};   // one pair per section (nestable)
   char name[256] = {0};
   int n_cu = 256;
-  double chunk_cap_gib = 0.0;        // posterior chunk cap of this context (api.hip: pick_chunk), set on first use
+  double chunk_cap_gib = 0.0;        // posterior chunk cap of this context (gp_posterior.hip: pick_chunk), set on first use
   // The next symmetric single-part Gram matrix is wanted as its lower triangle only (tiles on and below the diagonal;
   // the rest of the buffer is left as it is): the fit path, whose factorisation reads nothing above the diagonal.
   bool km_lower_only = false;
@@ -288,6 +288,9 @@ struct KernDev {
 };
 constexpr int ESP_MAX_ORDER = 32;      // register bucket of the ESP kernel-matrix kernel (kernmat.hip)
 constexpr int ESP_MAX_DIM = 256;       // one tile's columns of both operands in LDS
+// SE and Matern: k(x, x) does not depend on x (every other kind's prior variance comes from prior_diag)
+inline bool kind_is_stationary(int kind) { return kind == DFH_KERNEL_SE || kind == DFH_KERNEL_MATERN; }
+inline bool part_is_stationary(const KernDev& kd, int part) { return kind_is_stationary(kd.parts[part].kind); }
 int kerndev_build(dfh_ctx* ctx, const dfh_kernel_desc* k, KernDev* out);
 // host-only part of kerndev_build, and the upload of several descriptors with one copy into a
 // caller-provided device blob (kerndev_blob_bytes each, in order); such KernDevs own no memory

@@ -1,0 +1,146 @@
+// The GP object that lives in HBM and what its three units -- gp_fit.hip (fits, append, Gram-matrix posteriors),
+// gp_posterior.hip (chunked posterior, acquisitions) and gp_draw.hip (Thompson sampling, joint draws, multi-objective
+// calls) -- share.  Internal: include/dfhip.h is the contract.
+#pragma once
+#include "common.h"
+
+struct dfh_gp {
+  dfh_ctx* ctx = nullptr;
+  KernDev kd;
+  int64_t n = 0, d = 0, nblk = 0;
+  double noise_var = 0.0;
+  double diag_jitter = 0.0;      // what the ladder added on top of noise_var (0 if none)
+  double* Xp = nullptr;          // [n][P] packed scaled training inputs
+  double* Np = nullptr;          // [n][n_parts]
+  double* L = nullptr;           // [n][n] lower factor (strict upper part unspecified)
+  double* inv = nullptr;         // [2][nblk][NB][NB]: inverses of the diagonal blocks of L, then clean copies of the blocks
+  std::vector<int> refine;       // [nblk] refinement steps the solves take with each block (chol.hip: refine_steps)
+  double* alpha = nullptr;       // [n]
+  bool upper_zeroed = false;
+  bool gram = false;             // built from a host-evaluated Gram matrix: no kernel, no packed inputs
+  int psd_flags = 0;             // DFH_FIT_PROJECT_FIRST / DFH_FIT_TRY_BEFORE_PROJECT the fit ran under (L is not chol(K + noise I) of the kernel's K)
+};
+
+// state of the hallucinated augmentation (gp_core.py:192-220)
+struct Halluc {
+  int64_t q = 0;
+  double* Xhp = nullptr; double* Nhp = nullptr;   // packed Xh
+  double* Wt = nullptr;                           // [q][n] = K(Xh,X) L^-T
+  double* Lh = nullptr;                           // [q][q] chol(K_hh + noise I - Wt Wt^T)
+};
+
+#pragma GCC visibility push(hidden)      // what the units share: none of it joins the library's exported symbols
+
+// The points in progress of one call, resolved (halluc_resolve): the block form `h` on gp's own factor, or -- where
+// that is not positive definite, or gp's fit needed the ladder -- the augmented GP `aug` factored from scratch, which
+// this scope owns and frees.  With q == 0 neither: h.q == 0 and aug == nullptr.
+struct HallucScope {
+  Halluc h;
+  dfh_gp* gp = nullptr;
+  dfh_gp* aug = nullptr;
+  HallucScope() = default;
+  HallucScope(const HallucScope&) = delete;
+  HallucScope& operator=(const HallucScope&) = delete;
+  ~HallucScope() { if (aug) dfh_gp_free(aug); }
+  dfh_gp* cov_gp() const { return aug ? aug : gp; }          // whose factor the variances and covariances come from
+  int64_t block_q() const { return aug ? 0 : h.q; }          // rows of the second block row (0: there is none)
+  const Halluc* block() const { return block_q() > 0 ? &h : nullptr; }
+};
+
+// One chunk of the posterior (posterior_chunk): which parts of the kernel, and what besides the mean.
+struct ChunkReq {
+  int part_lo = 0, part_hi = -1;        // part range (-1: all of the kernel's)
+  bool pre_gathered = false;            // Xs holds only the columns of part_lo (the add-UCB group path)
+  bool want_var = true;                 // solve the cross matrix into V^T (and fill ss / ss2)
+  const Halluc* h = nullptr;            // block form of the points in progress: the second block row as well
+  int parity = 0;                       // which set of chunk buffers (the pipelined Thompson sampling alternates)
+};
+struct ChunkOut {                       // where posterior_chunk left things (scratch of the request's parity)
+  double* Xsp = nullptr; double* Nsp = nullptr;   // the packed candidates
+  double* Kct = nullptr;                // cross matrix, V^T once solved
+  double* T = nullptr;                  // V2^T: the rows solved against Lh (block form only)
+};
+
+// Packed candidates in one scratch block: Xsp [rows][P] at its start, Nsp [rows][n_parts] behind it on a 256-byte boundary
+struct PackedXs { size_t nsp_off, bytes; };
+inline PackedXs packed_xs_layout(const KernDev& kd, int64_t rows) {
+  const size_t b_xsp = ((size_t)rows * kd.P * 8 + 255) / 256 * 256;
+  return PackedXs{b_xsp, b_xsp + (size_t)rows * kd.n_parts * 8};
+}
+
+// What gp_eval_driver is asked for (predict, acquisition arg-max, add-UCB of one group)
+struct EvalReq {
+  int acq = DFH_ACQ_MEAN;
+  const double* params = nullptr;                 // the acquisition's two parameters (null: zeros)
+  const double* Xs = nullptr;                     // candidates [m][ldxs], host or device
+  int64_t m = 0, ldxs = 0;
+  int part_lo = 0, part_hi = -1;                  // as ChunkReq
+  bool pre_gathered = false;
+  double kxx = 0.0;                               // prior variance of a stationary part range
+  const double* Xh = nullptr; int64_t q = 0;      // points in progress
+  double mean_const = 0.0;
+  const double* mean_vals = nullptr;              // per candidate (host or device), instead of mean_const
+  bool want_var = true;
+  double* mu_out = nullptr; double* sd_out = nullptr; double* vals_out = nullptr;     // [m] each, optional
+  double* best_val = nullptr; int64_t* best_idx = nullptr;                            // the winner, optional
+};
+
+// Running winner of an arg-max over chunks (numpy argmax ordering: a NaN beats everything, earlier index wins ties)
+struct Winner {
+  bool have = false; double v = 0.0; int64_t i = -1;
+  void merge(double ov, int64_t oi);
+  int update(dfh_ctx* ctx, const double* vals, int64_t mc, int64_t i0);    // arg-max of vals[0..mc) (device), indices from i0; synchronises
+  void store(double* best_val, int64_t* best_idx) const {
+    if (best_val) *best_val = v;
+    if (best_idx) *best_idx = i;
+  }
+};
+
+// The candidates and their prior means chunk by chunk, wherever the caller keeps them: a device pointer is offset, a host
+// pointer staged (Xs through `slot`, which the pipelined Thompson sampling alternates; the means through SCR_STAGE_D).
+struct ChunkStager {
+  dfh_ctx* ctx = nullptr; const double* Xs = nullptr; int64_t ldxs = 0; const double* mean_vals = nullptr;
+  bool xs_dev = true, mv_dev = true;
+  ChunkStager() = default;
+  ChunkStager(dfh_ctx* c, const double* Xs_, int64_t ldxs_, const double* mean_vals_)
+      : ctx(c), Xs(Xs_), ldxs(ldxs_), mean_vals(mean_vals_), xs_dev(Xs_ ? is_device_ptr(Xs_) : true),
+        mv_dev(mean_vals_ ? is_device_ptr(mean_vals_) : true) {}
+  int xs(int64_t i0, int64_t mc, int slot, const double** out) const {
+    if (xs_dev) { *out = Xs + i0 * ldxs; return DFH_OK; }
+    return to_device(ctx, Xs + i0 * ldxs, (size_t)mc * ldxs * 8, slot, out);
+  }
+  int mean(int64_t i0, int64_t mc, const double** out) const {             // *out = nullptr without mean_vals
+    *out = nullptr;
+    if (!mean_vals) return DFH_OK;
+    if (mv_dev) { *out = mean_vals + i0; return DFH_OK; }
+    return to_device(ctx, mean_vals + i0, (size_t)mc * 8, SCR_STAGE_D, out);
+  }
+};
+
+struct DevBlock {           // dev_alloc'ed memory of one call
+  dfh_ctx* ctx; void* p = nullptr;
+  explicit DevBlock(dfh_ctx* c) : ctx(c) {}
+  ~DevBlock() {             // (a block goes back to the cache only once nothing in flight can touch it)
+    if (!p) return;
+    (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->bulk);
+    dev_release(ctx, p);
+  }
+};
+
+// gp_posterior.hip
+bool free_plus_own_scratch(dfh_ctx* ctx, size_t* bytes);     // free device memory + the context's own scratch; false: unknown
+int64_t pick_chunk(dfh_ctx* ctx, int64_t n, int64_t m);      // candidate rows per posterior chunk
+int halluc_resolve(dfh_gp* gp, const double* Xh, int64_t q, HallucScope* s);
+// One chunk of candidates (device pointer Xs_dev, mc rows): fills mu_raw, ss (and ss2 with rq.h)
+int posterior_chunk(dfh_gp* gp, const double* Xs_dev, int64_t mc, int64_t ldxs, const ChunkReq& rq, double* mu_raw,
+                    double* ss, double* ss2, ChunkOut* out = nullptr);
+__global__ void k_argmax_rows(const double* __restrict__ v, long ld, long m, double* __restrict__ out_v,
+                              long* __restrict__ out_i);
+__global__ void k_posterior_acq(int acq, double p0, double p1, double kxx, const double* __restrict__ kss,
+                                double mean_const, const double* __restrict__ mean_vals, const double* __restrict__ mu_raw,
+                                const double* __restrict__ ss, const double* __restrict__ ss2, long m,
+                                double* __restrict__ mu_out, double* __restrict__ sd_out,
+                                double* __restrict__ val_out);
+// gp_draw.hip
+__global__ void k_add_vec(double* __restrict__ y, const double* __restrict__ a, double c, long n);
+#pragma GCC visibility pop

@@ -1112,8 +1112,6 @@ static int make_part(KernDev* kd, int kind, double scale, double nu, const int* 
   return DFH_OK;
 }
 
-static bool kind_is_stationary(int kind) { return kind == DFH_KERNEL_SE || kind == DFH_KERNEL_MATERN; }
-
 int kerndev_build_host(const dfh_kernel_desc* k, KernDev* kd) {
   DFH_ARG(k != nullptr && kd != nullptr);
   DFH_ARG(k->dim >= 1);

@@ -1,5 +1,5 @@
 """MI355X: from n = 2048 on the fit writes the 64 x 64 tiles on and below the diagonal of K + noise I only (round 5;
-csrc/api.hip: dfh_gp_fit, _get_training_kernel_matrix + stable_cholesky of dragonfly/gp/gp_core.py:155-160, 827-847) and
+csrc/gp_fit.hip: dfh_gp_fit, _get_training_kernel_matrix + stable_cholesky of dragonfly/gp/gp_core.py:155-160, 827-847) and
 the tiles above keep what the recycled buffer held.  Nothing may read them: with the buffer filled with NaN first
 (DFH_TEST_POISON_L=1) the factor, alpha, lml, GP.eval, the hallucinated posterior, a joint Thompson block and an append
 are the same as with the full symmetric build (DFH_KM_LOWER_ONLY=0) -- at a size that is a multiple of the tiles and at
