@@ -6,20 +6,13 @@
 #endif
 
 // ---------------------------------------------------------------------------------------------
-extern "C" int dfh_kernel_matrix(dfh_ctx* ctx, const dfh_kernel_desc* k, const double* X1, int64_t n1,
-                                 const double* X2, int64_t n2, double diag_add, double* K_out) {
-  DFH_ARG(ctx && k && K_out);
-  DFH_ARG(n1 >= 0 && (X2 == nullptr || n2 >= 0));
+// What dfh_kernel_matrix and dfh_dist_squared share: stage X1 (and X2, null for the symmetric case), pack them for kd,
+// let `build` make the matrix on the device from the packed points (the same twice: symmetric) and copy it back;
+// kd is freed.
+static int matrix_of_inputs(dfh_ctx* ctx, KernDev& kd, int64_t d, const double* X1, int64_t n1, const double* X2, int64_t n2,
+                            double* out, const std::function<int(KmPts, KmPts, double*)>& build) {
   const bool sym = (X2 == nullptr);
-  if (sym) n2 = n1;
-  if (n1 == 0 || n2 == 0) return DFH_OK;     // kernel.py:81-82: empty result
-  DFH_ARG(X1 != nullptr);
-  DFH_HIP(hipSetDevice(ctx->device));
-  KernDev kd;
-  int rc = kerndev_build(ctx, k, &kd);
-  if (rc != DFH_OK) { kerndev_free(&kd); return rc; }
   auto body = [&]() -> int {
-    const int64_t d = k->dim;
     const double *dX1 = nullptr, *dX2 = nullptr;
     DFH_TRY(to_device(ctx, X1, (size_t)n1 * d * 8, SCR_STAGE_A, &dX1));
     if (!sym) DFH_TRY(to_device(ctx, X2, (size_t)n2 * d * 8, SCR_STAGE_B, &dX2));
@@ -33,20 +26,36 @@ extern "C" int dfh_kernel_matrix(dfh_ctx* ctx, const dfh_kernel_desc* k, const d
     double* Np2 = sym ? Np1 : reinterpret_cast<double*>(buf + b1 + bn1 + b2);
     DFH_TRY(pack_scaled(ctx, kd, 0, kd.n_parts, false, dX1, n1, d, Xp1, Np1));
     if (!sym) DFH_TRY(pack_scaled(ctx, kd, 0, kd.n_parts, false, dX2, n2, d, Xp2, Np2));
-    const bool dev_out = is_device_ptr(K_out);
-    double* Kd = K_out;
+    const bool dev_out = is_device_ptr(out);
+    double* Kd = out;
     if (!dev_out) DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)n1 * n2 * 8, (void**)&Kd));
-    {
-      SectionTimer t(ctx, sym ? DFH_T_KERNMAT : DFH_T_CROSS);
-      DFH_TRY(kernmat_packed(ctx, kd, 0, kd.n_parts, true, Xp1, Np1, n1, Xp2, Np2, n2, sym, diag_add, Kd, n2));
-    }
-    if (!dev_out) DFH_TRY(from_device(ctx, K_out, Kd, (size_t)n1 * n2 * 8));
+    DFH_TRY(build(KmPts{Xp1, Np1, n1}, KmPts{Xp2, Np2, n2}, Kd));
+    if (!dev_out) DFH_TRY(from_device(ctx, out, Kd, (size_t)n1 * n2 * 8));
     return DFH_OK;
   };
-  rc = body();
+  const int rc = body();
   (void)hipStreamSynchronize(ctx->stream);
   kerndev_free(&kd);
   return rc;
+}
+
+extern "C" int dfh_kernel_matrix(dfh_ctx* ctx, const dfh_kernel_desc* k, const double* X1, int64_t n1,
+                                 const double* X2, int64_t n2, double diag_add, double* K_out) {
+  DFH_ARG(ctx && k && K_out);
+  DFH_ARG(n1 >= 0 && (X2 == nullptr || n2 >= 0));
+  const bool sym = (X2 == nullptr);
+  if (sym) n2 = n1;
+  if (n1 == 0 || n2 == 0) return DFH_OK;     // kernel.py:81-82: empty result
+  DFH_ARG(X1 != nullptr);
+  DFH_HIP(hipSetDevice(ctx->device));
+  KernDev kd;
+  const int rc = kerndev_build(ctx, k, &kd);
+  if (rc != DFH_OK) { kerndev_free(&kd); return rc; }
+  return matrix_of_inputs(ctx, kd, k->dim, X1, n1, X2, n2, K_out, [&](KmPts p1, KmPts p2, double* Kd) -> int {
+    SectionTimer t(ctx, sym ? DFH_T_KERNMAT : DFH_T_CROSS);
+    if (sym) return kernmat_gram(ctx, kd, 0, kd.n_parts, true, p1, diag_add, Kd, n2);
+    return kernmat_cross(ctx, kd, 0, kd.n_parts, true, p1, p2, Kd, n2);
+  });
 }
 
 extern "C" int dfh_dist_squared(dfh_ctx* ctx, const double* X1, int64_t n1, const double* X2, int64_t n2,
@@ -56,33 +65,11 @@ extern "C" int dfh_dist_squared(dfh_ctx* ctx, const double* X1, int64_t n1, cons
   DFH_ARG(X1 && X2);
   DFH_HIP(hipSetDevice(ctx->device));
   KernDev kd;
-  int rc = kerndev_build_dist(ctx, (int)d, &kd);
+  const int rc = kerndev_build_dist(ctx, (int)d, &kd);
   if (rc != DFH_OK) { kerndev_free(&kd); return rc; }
-  auto body = [&]() -> int {
-    const double *dX1 = nullptr, *dX2 = nullptr;
-    DFH_TRY(to_device(ctx, X1, (size_t)n1 * d * 8, SCR_STAGE_A, &dX1));
-    DFH_TRY(to_device(ctx, X2, (size_t)n2 * d * 8, SCR_STAGE_B, &dX2));
-    char* buf = nullptr;
-    const size_t b1 = ((size_t)n1 * kd.P * 8 + 255) / 256 * 256, bn1 = ((size_t)n1 * 8 + 255) / 256 * 256;
-    const size_t b2 = ((size_t)n2 * kd.P * 8 + 255) / 256 * 256, bn2 = (size_t)n2 * 8;
-    DFH_TRY(scratch_get(ctx, SCR_XS, b1 + bn1 + b2 + bn2 + 256, (void**)&buf));
-    double* Xp1 = reinterpret_cast<double*>(buf);
-    double* Np1 = reinterpret_cast<double*>(buf + b1);
-    double* Xp2 = reinterpret_cast<double*>(buf + b1 + bn1);
-    double* Np2 = reinterpret_cast<double*>(buf + b1 + bn1 + b2);
-    DFH_TRY(pack_scaled(ctx, kd, 0, 1, false, dX1, n1, d, Xp1, Np1));
-    DFH_TRY(pack_scaled(ctx, kd, 0, 1, false, dX2, n2, d, Xp2, Np2));
-    const bool dev_out = is_device_ptr(D_out);
-    double* Kd = D_out;
-    if (!dev_out) DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)n1 * n2 * 8, (void**)&Kd));
-    DFH_TRY(kernmat_packed(ctx, kd, 0, 1, false, Xp1, Np1, n1, Xp2, Np2, n2, false, 0.0, Kd, n2));
-    if (!dev_out) DFH_TRY(from_device(ctx, D_out, Kd, (size_t)n1 * n2 * 8));
-    return DFH_OK;
-  };
-  rc = body();
-  (void)hipStreamSynchronize(ctx->stream);
-  kerndev_free(&kd);
-  return rc;
+  return matrix_of_inputs(ctx, kd, d, X1, n1, X2, n2, D_out, [&](KmPts p1, KmPts p2, double* Kd) -> int {
+    return kernmat_cross(ctx, kd, 0, 1, false, p1, p2, Kd, n2);
+  });
 }
 
 extern "C" int dfh_gemm(dfh_ctx* ctx, int transb, int64_t M, int64_t N, int64_t K, double alpha,

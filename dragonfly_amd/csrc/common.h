@@ -92,9 +92,6 @@ struct dfh_ctx {
   char name[256] = {0};
   int n_cu = 256;
   double chunk_cap_gib = 0.0;        // posterior chunk cap of this context (gp_posterior.hip: pick_chunk), set on first use
-  // The next symmetric single-part Gram matrix is wanted as its lower triangle only (tiles on and below the diagonal;
-  // the rest of the buffer is left as it is): the fit path, whose factorisation reads nothing above the diagonal.
-  bool km_lower_only = false;
   // Extended GEMM launches of the factorisation (gemm_f64.hip, chol.hip), consumed by the next
   // gemm_f64 call(s) while set: a device-side skip condition (the launch exits unless *gemm_cond >
   // gemm_cond_thr) and the look-ahead tile order with its completion counters.
@@ -254,7 +251,7 @@ struct PartDev {
 constexpr int FM_IN = 4, FM_BEGIN = 1, FM_END = 2;
 constexpr int EXPDECAY_MAX_DIM = 8;
 constexpr int HAMMING_MAX_DIM = 32;    // one operand chunk of the kernel-matrix kernel (KM_KC); one level of NumPy's pairwise sum
-// where the weights of the Hamming columns sit in a kernel's device image (kernmat.hip: blob_layout), from its start
+// where the weights of the Hamming columns sit in a kernel's device image (kerndev.hip: blob_layout), from its start
 __host__ __device__ inline size_t blob_hw_offset(int n_parts, int P) {
   const size_t p = P ? P : 1;
   const size_t a16 = 15;
@@ -279,14 +276,14 @@ struct KernDev {
   double kxx = 0.0;            // prior variance k(x,x) of a stationary kernel
   bool stationary = true;      // false with a Poly / ExpDecay / Hamming part: the SE / Matern-only kernels do not apply, and
                                // k(x,x) comes from prior_diag (it depends on x for Poly / ExpDecay; a Hamming part's is its k0)
-  bool hamming = false;        // some part is a Hamming kernel: the kernel-matrix instances that know the compare (kernmat.hip)
+  bool hamming = false;        // some part is a Hamming kernel: the kernel-matrix instances that know the compare (km_generic.hip)
   // ESP kernel (DFH_KERNEL_ESP): one SE / Matern part per column, combined by Newton-Girard into the
   // elementary symmetric polynomial of order esp_order, times outer_scale.  multi is set (several parts)
   // and product is not: every consumer of multi / product must test esp first.
   bool esp = false;
   int esp_order = 0;
 };
-constexpr int ESP_MAX_ORDER = 32;      // register bucket of the ESP kernel-matrix kernel (kernmat.hip)
+constexpr int ESP_MAX_ORDER = 32;      // register bucket of the ESP kernel-matrix kernel (km_esp.hip)
 constexpr int ESP_MAX_DIM = 256;       // one tile's columns of both operands in LDS
 // SE and Matern: k(x, x) does not depend on x (every other kind's prior variance comes from prior_diag)
 inline bool kind_is_stationary(int kind) { return kind == DFH_KERNEL_SE || kind == DFH_KERNEL_MATERN; }
@@ -350,14 +347,18 @@ int kernmat_sym_batch(dfh_ctx* ctx, const KernDev& kd, int count, int64_t sBlob,
                       int64_t sXp, const double* Np, int64_t sNp, int64_t n, const double* d_diag_adds,
                       double* K, int64_t sK, int64_t ldk);
 
-// K[n1 x n2] (ldk) = sum over parts [part_lo,part_hi) of k_part (times outer scale if multi).
-// symmetric: Xp2/Np2 == Xp1/Np1 and diag_add is added on the diagonal.
-int kernmat_packed(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bool apply_outer,
-                   const double* Xp1, const double* Np1, int64_t n1, const double* Xp2,
-                   const double* Np2, int64_t n2, bool symmetric, double diag_add, double* K,
-                   int64_t ldk, const double* mu_alpha = nullptr, double* mu_out = nullptr, bool* mu_done = nullptr);
-// (mu_alpha, mu_out, mu_done: ask for mu_out[n1] = K mu_alpha from the same pass; *mu_done tells whether
-//  the kernel that ran could do it -- the caller multiplies itself otherwise)
+// K (ldk) = sum over parts [part_lo, part_hi) of k_part (times outer scale if multi) between packed points
+// (pack_scaled: Xp[n][P], Np[n][n_parts]).
+struct KmPts { const double* Xp; const double* Np; int64_t n; };
+// kernmat_gram: K(pts, pts) + diag_add I.  lower_only: the tiles on and below the diagonal suffice (the fit, whose
+// factorisation reads nothing above it); the kernels that can then leave the rest of the buffer as it is.
+int kernmat_gram(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bool apply_outer, KmPts pts, double diag_add,
+                 double* K, int64_t ldk, bool lower_only = false);
+// kernmat_cross: K(pts1, pts2).  mean: out[pts1.n] = K alpha is wanted from the same pass; done tells whether the kernel
+// that ran could do it -- the caller multiplies itself otherwise.
+struct KmMean { const double* alpha; double* out; bool done; };
+int kernmat_cross(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bool apply_outer, KmPts pts1, KmPts pts2,
+                  double* K, int64_t ldk, KmMean* mean = nullptr);
 
 // Blocked Cholesky, in place on the lower triangle of the row-major matrix A (upper part of the
 // off-diagonal blocks is left untouched; the upper part of the 64x64 diagonal blocks is zeroed).

@@ -260,7 +260,7 @@ int ts_sigma_kernel(TsRun& r, int64_t b0, int64_t B, double* dst) {
   const KernDev& kd = r.cov_gp->kd;
   const double* Xbp = r.st[r.p].co.Xsp + b0 * kd.P;
   const double* Nbp = r.st[r.p].co.Nsp + b0 * kd.n_parts;
-  return kernmat_packed(r.ctx, kd, 0, kd.n_parts, true, Xbp, Nbp, B, Xbp, Nbp, B, true, 0.0, dst, B);
+  return kernmat_gram(r.ctx, kd, 0, kd.n_parts, true, KmPts{Xbp, Nbp, B}, 0.0, dst, B);
 }
 
 int ts_single_block(TsRun& r, int64_t b0, int64_t B, double* dst, int64_t bidx) {

@@ -109,14 +109,11 @@ extern "C" int dfh_gp_fit(dfh_ctx* ctx, const dfh_kernel_desc* k, const double* 
     static const bool poison_l = env_flag("DFH_TEST_POISON_L", false);
     auto build_M = [&]() -> int {     // K + noise_var * I     (gp_core.py:843)
       SectionTimer t(ctx, DFH_T_KERNMAT);
-      ctx->km_lower_only = lower_env && n >= 2048;
       // test hook (tests/test_gpu_upper_triangle_unread.py): the buffer comes recycled from the pool, and with the
       // lower-triangle-only build the tiles above the diagonal keep whatever it held -- correctness rests on no schedule
       // of the factorisation or the solves ever reading them.  DFH_TEST_POISON_L=1 fills the buffer with NaN first.
       if (poison_l) DFH_HIP(hipMemsetAsync(gp->L, 0xFF, (size_t)n * n * 8, ctx->stream));
-      const int rc = kernmat_packed(ctx, kd, 0, kd.n_parts, true, gp->Xp, gp->Np, n, gp->Xp, gp->Np, n, true, noise_var, gp->L, n);
-      ctx->km_lower_only = false;
-      return rc;
+      return kernmat_gram(ctx, kd, 0, kd.n_parts, true, KmPts{gp->Xp, gp->Np, n}, noise_var, gp->L, n, lower_env && n >= 2048);
     };
     {
       SectionTimer t(ctx, DFH_T_KERNMAT);
@@ -130,7 +127,7 @@ extern "C" int dfh_gp_fit(dfh_ctx* ctx, const dfh_kernel_desc* k, const double* 
       DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)n * n * 8, (void**)&Kw));
       {
         SectionTimer t(ctx, DFH_T_KERNMAT);
-        DFH_TRY(kernmat_packed(ctx, kd, 0, kd.n_parts, true, gp->Xp, gp->Np, n, gp->Xp, gp->Np, n, true, 0.0, Kw, n));
+        DFH_TRY(kernmat_gram(ctx, kd, 0, kd.n_parts, true, KmPts{gp->Xp, gp->Np, n}, 0.0, Kw, n));
       }
       DFH_TRY(factor_gram_psd(gp, Kw, flags, jitter_power));
       return gp_alpha_and_lml(gp, dy, lml);
@@ -319,14 +316,13 @@ extern "C" int dfh_gp_append(dfh_gp* gp, const double* Xnew, int64_t q, const do
         DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)n2 * n2 * 8, (void**)&Kw));
         {
           SectionTimer t(ctx, DFH_T_KERNMAT);
-          DFH_TRY(kernmat_packed(ctx, kd, 0, parts, true, g2->Xp, g2->Np, n2, g2->Xp, g2->Np, n2, true, 0.0, Kw, n2));
+          DFH_TRY(kernmat_gram(ctx, kd, 0, parts, true, KmPts{g2->Xp, g2->Np, n2}, 0.0, Kw, n2));
         }
         return factor_gram_psd(g2, Kw, gp->psd_flags | (flags & DFH_FIT_NO_JITTER), jitter_power);
       }
       auto build_M = [&]() -> int {
         SectionTimer t(ctx, DFH_T_KERNMAT);
-        return kernmat_packed(ctx, kd, 0, parts, true, g2->Xp, g2->Np, n2, g2->Xp, g2->Np, n2, true,
-                              g2->noise_var, g2->L, n2);
+        return kernmat_gram(ctx, kd, 0, parts, true, KmPts{g2->Xp, g2->Np, n2}, g2->noise_var, g2->L, n2);
       };
       DFH_TRY(build_M());
       SectionTimer t(ctx, DFH_T_CHOL);
@@ -340,7 +336,7 @@ extern "C" int dfh_gp_append(dfh_gp* gp, const double* Xnew, int64_t q, const do
       DFH_TRY(copy_matrix(ctx, gp->L, n, g2->L, n2, n, n));
       {
         SectionTimer t(ctx, DFH_T_CROSS);
-        DFH_TRY(kernmat_packed(ctx, kd, 0, parts, true, Xpn, Npn, q, g2->Xp, g2->Np, n, false, 0.0, Bm, n2));
+        DFH_TRY(kernmat_cross(ctx, kd, 0, parts, true, KmPts{Xpn, Npn, q}, KmPts{g2->Xp, g2->Np, n}, Bm, n2));
       }
       {
         SectionTimer t(ctx, DFH_T_TRSM);
@@ -349,7 +345,7 @@ extern "C" int dfh_gp_append(dfh_gp* gp, const double* Xnew, int64_t q, const do
       {
         SectionTimer t(ctx, DFH_T_CHOL);
         const std::function<int()> build_S = [&]() -> int {
-          DFH_TRY(kernmat_packed(ctx, kd, 0, parts, true, Xpn, Npn, q, Xpn, Npn, q, true, g2->noise_var, S, n2));
+          DFH_TRY(kernmat_gram(ctx, kd, 0, parts, true, KmPts{Xpn, Npn, q}, g2->noise_var, S, n2));
           return gemm_f64(ctx, GEMM_LOWER, q, q, n, -1.0, Bm, n2, Bm, n2, 1.0, S, n2, S, n2);
         };
         DFH_TRY(build_S());
@@ -398,7 +394,7 @@ extern "C" int dfh_gp_get(dfh_gp* gp, int what, double* out) {
     const bool dev_out = is_device_ptr(out);
     double* Kd = out;
     if (!dev_out) DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)n * n * 8, (void**)&Kd));
-    DFH_TRY(kernmat_packed(ctx, gp->kd, 0, gp->kd.n_parts, true, gp->Xp, gp->Np, n, gp->Xp, gp->Np, n, true, 0.0, Kd, n));
+    DFH_TRY(kernmat_gram(ctx, gp->kd, 0, gp->kd.n_parts, true, KmPts{gp->Xp, gp->Np, n}, 0.0, Kd, n));
     if (!dev_out) DFH_TRY(from_device(ctx, out, Kd, (size_t)n * n * 8));
     return DFH_OK;
   }

@@ -299,11 +299,11 @@ int halluc_prepare(dfh_gp* gp, const double* Xh_user, int64_t q, Halluc* h) {
   h->Lh = reinterpret_cast<double*>(reinterpret_cast<char*>(h->Wt) + ((b_wt + 255) / 256) * 256);
   DFH_TRY(pack_scaled(ctx, kd, 0, kd.n_parts, false, Xh, q, gp->d, h->Xhp, h->Nhp));
   // Wt = K(Xh, X) L^-T
-  DFH_TRY(kernmat_packed(ctx, kd, 0, kd.n_parts, true, h->Xhp, h->Nhp, q, gp->Xp, gp->Np, gp->n, false, 0.0, h->Wt, gp->n));
+  DFH_TRY(kernmat_cross(ctx, kd, 0, kd.n_parts, true, KmPts{h->Xhp, h->Nhp, q}, KmPts{gp->Xp, gp->Np, gp->n}, h->Wt, gp->n));
   DFH_TRY(trsm_rows(ctx, gp->L, gp->n, gp->n, gp->inv, h->Wt, q, gp->n, gp->refine.data()));
   // S = K(Xh,Xh) + (noise + jitter) I - Wt Wt^T ; Lh = chol(S)
   const std::function<int()> build_S = [&]() -> int {
-    DFH_TRY(kernmat_packed(ctx, kd, 0, kd.n_parts, true, h->Xhp, h->Nhp, q, h->Xhp, h->Nhp, q, true, gp->noise_var, h->Lh, q));
+    DFH_TRY(kernmat_gram(ctx, kd, 0, kd.n_parts, true, KmPts{h->Xhp, h->Nhp, q}, gp->noise_var, h->Lh, q));
     return gemm_f64(ctx, 0, q, q, gp->n, -1.0, h->Wt, gp->n, h->Wt, gp->n, 1.0, h->Lh, q, h->Lh, q);
   };
   DFH_TRY(build_S());
@@ -325,7 +325,7 @@ int halluc_second_row(dfh_gp* gp, const Halluc& h, const double* Xsp, const doub
   double* T = nullptr;
   DFH_TRY(scratch_get(ctx, slot, (size_t)rows * q * 8, (void**)&T));
   // T = k(Xs, Xh) - V1t Wt^T
-  DFH_TRY(kernmat_packed(ctx, kd, 0, kd.n_parts, true, Xsp, Nsp, rows, h.Xhp, h.Nhp, q, false, 0.0, T, q));
+  DFH_TRY(kernmat_cross(ctx, kd, 0, kd.n_parts, true, KmPts{Xsp, Nsp, rows}, KmPts{h.Xhp, h.Nhp, q}, T, q));
   DFH_TRY(gemm_f64(ctx, 0, rows, q, gp->n, -1.0, Kct, gp->n, h.Wt, gp->n, 1.0, T, q, T, q));
   hipLaunchKernelGGL(k_halluc_rows, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, T, (long)rows, (int)q, h.Lh, ss2);
   DFH_LAUNCH_CHECK();
@@ -370,10 +370,10 @@ int posterior_chunk(dfh_gp* gp, const double* Xs_dev, int64_t mc, int64_t ldxs, 
   {
     SectionTimer t(ctx, DFH_T_CROSS);
     DFH_TRY(pack_scaled(ctx, kd, rq.part_lo, part_hi, rq.pre_gathered, Xs_dev, mc, ldxs, o.Xsp, o.Nsp));
-    bool mu_done = false;      // gp_core.py:174, from the same pass where the kernel can
-    DFH_TRY(kernmat_packed(ctx, kd, rq.part_lo, part_hi, true, o.Xsp, o.Nsp, mc, gp->Xp, gp->Np, gp->n, false, 0.0, o.Kct, gp->n,
-                           gp->alpha, mu_raw, &mu_done));
-    if (!mu_done) DFH_TRY(gemv_rows(ctx, o.Kct, mc, gp->n, gp->n, gp->alpha, 1.0, nullptr, 0.0, mu_raw));
+    KmMean mean{gp->alpha, mu_raw, false};      // gp_core.py:174, from the same pass where the kernel can
+    DFH_TRY(kernmat_cross(ctx, kd, rq.part_lo, part_hi, true, KmPts{o.Xsp, o.Nsp, mc}, KmPts{gp->Xp, gp->Np, gp->n}, o.Kct, gp->n,
+                          &mean));
+    if (!mean.done) DFH_TRY(gemv_rows(ctx, o.Kct, mc, gp->n, gp->n, gp->alpha, 1.0, nullptr, 0.0, mu_raw));
   }
   if (rq.want_var) {
     {
@@ -557,10 +557,10 @@ extern "C" int dfh_gp_add_ucb_all(dfh_gp* gp, const double* betas, const double*
       double* Xsp_g = Xsp + off[g] * kd.P; double* Nsp_g = Nsp + off[g] * kd.n_parts;
       DFH_TRY(pack_scaled(ctx, kd, g, g + 1, true, dXg + xoff[g], m_per_group[g], gdim[g], Xsp_g, Nsp_g));
       // K_j(X*_j, X[:, group j]) with the outer scale        (gpb_acquisitions.py:166-168)
-      bool mu_done = false;
-      DFH_TRY(kernmat_packed(ctx, kd, g, g + 1, true, Xsp_g, Nsp_g, m_per_group[g], gp->Xp, gp->Np, n, false,
-                             0.0, Kct + off[g] * n, n, gp->alpha, mu_raw + off[g], &mu_done));
-      mu_all = mu_all && mu_done;
+      KmMean mean{gp->alpha, mu_raw + off[g], false};
+      DFH_TRY(kernmat_cross(ctx, kd, g, g + 1, true, KmPts{Xsp_g, Nsp_g, m_per_group[g]}, KmPts{gp->Xp, gp->Np, n},
+                            Kct + off[g] * n, n, &mean));
+      mu_all = mu_all && mean.done;
     }
     if (!mu_all) DFH_TRY(gemv_rows(ctx, Kct, M, n, n, gp->alpha, 1.0, nullptr, 0.0, mu_raw));
   }
@@ -628,7 +628,7 @@ extern "C" int dfh_gp_predict_covar(dfh_gp* gp, const double* Xs, int64_t m, con
   const bool dev_out = is_device_ptr(cov_out);
   double* C = cov_out;
   if (!dev_out) DFH_TRY(scratch_get(ctx, SCR_TSK, (size_t)m * m * 8, (void**)&C));
-  DFH_TRY(kernmat_packed(ctx, kd, 0, kd.n_parts, true, co.Xsp, co.Nsp, m, co.Xsp, co.Nsp, m, true, 0.0, C, m));
+  DFH_TRY(kernmat_gram(ctx, kd, 0, kd.n_parts, true, KmPts{co.Xsp, co.Nsp, m}, 0.0, C, m));
   DFH_TRY(gemm_f64(ctx, 0, m, m, gp->n, -1.0, co.Kct, gp->n, co.Kct, gp->n, 1.0, C, m, C, m));
   if (hs.block_q() > 0) {
     // second block row of the augmented solve: V2t = (k(Xs,Xh) - V1t Wt^T) Lh^-T ; cov -= V2t V2t^T

@@ -1,6 +1,6 @@
 // Kernel evaluation on the device: exp / sqrt for the arguments a stationary kernel produces, one part's value from a
 // squared distance (kern_eval), the polynomial / exponential-decay / Hamming parts, the combination rule of a product kernel with
-// additive factors, NumPy's pairwise row sum of squares.  Shared by kernmat.hip (the kernel-matrix kernels), lml_tiny.hip (the tuning
+// additive factors, NumPy's pairwise row sum of squares.  Shared by kernmat.h (the kernel-matrix kernels of the km_*.hip units), lml_tiny.hip (the tuning
 // objective of small problems) and lml_wg.h (the one-workgroup tuning objective with its Gram matrix built in the same
 // launch).  Include inside the translation unit's anonymous namespace.
 #pragma once

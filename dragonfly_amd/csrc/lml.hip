@@ -243,7 +243,7 @@ int build_group_grams(dfh_ctx* ctx, const std::vector<KernDev>& kds, int g, cons
   for (int c = 0; c < g; ++c) {
     double* Xp = Xpb + c * sXp; double* Np = Npb + c * sNp;
     DFH_TRY(pack_scaled(ctx, kds[c], 0, kds[c].n_parts, false, dX, n, d, Xp, Np));
-    DFH_TRY(kernmat_packed(ctx, kds[c], 0, kds[c].n_parts, true, Xp, Np, n, Xp, Np, n, true, h_noise[c], K + c * sK, ldK));
+    DFH_TRY(kernmat_gram(ctx, kds[c], 0, kds[c].n_parts, true, KmPts{Xp, Np, n}, h_noise[c], K + c * sK, ldK));
   }
   return DFH_OK;
 }
@@ -290,8 +290,8 @@ int lml_batch_lockstep(const LmlCall& a) {
     DFH_HIP(hipMemcpyAsync(dpar, hpar.data(), (size_t)g * 16, hipMemcpyHostToDevice, ctx->stream));
     auto build_M = [&](int c) -> int {           // K + noise_var * I again, from the packed inputs (a failed factorisation destroys it)
       double* Xp = Xpb + c * sXp; double* Np = Npb + c * sNp;
-      return kernmat_packed(ctx, kds[c], 0, kds[c].n_parts, true, Xp, Np, n, Xp, Np, n, true,
-                            a.noise_vars[c0 + c], Kb + c * strideK, ldK);
+      return kernmat_gram(ctx, kds[c], 0, kds[c].n_parts, true, KmPts{Xp, Np, n}, a.noise_vars[c0 + c], Kb + c * strideK,
+                          ldK);
     };
     {
       SectionTimer t(ctx, DFH_T_KERNMAT);

@@ -5,7 +5,7 @@ categorical ones, and the Cartesian-product kernel over the parts of a mixed dom
 Host-side counterpart of dragonfly/gp/kernel.py: the class names, constructor arguments, the
 `hyperparams` dictionary, the printed form and the error behaviour are the reference's (its lines
 are quoted in the docstrings), so code written against the reference's kernels runs unchanged.
-The Gram / cross matrices themselves are produced by libdfhip.so (csrc/kernmat.hip) -- there is no
+The Gram / cross matrices themselves are produced by libdfhip.so (csrc/kernmat.hip and the km_*.hip units) -- there is no
 NumPy evaluation path here, except for grouped kernels with a factor the device does not know,
 which are composed from their factors' own evaluations.
 """
@@ -475,7 +475,7 @@ class CoordinateProductKernel(_GroupedKernel):
     return K
 
 
-# Orders above this stay in host-kernel mode: the device keeps the power sums in registers (csrc/kernmat.hip), and at
+# Orders above this stay in host-kernel mode: the device keeps the power sums in registers (csrc/km_esp.hip), and at
 # such orders the reference's Newton-Girard recursion is dominated by cancellation in fp64 anyway.
 ESP_DEVICE_MAX_ORDER = 32
 ESP_DEVICE_MAX_DIM = 256

@@ -1,4 +1,4 @@
-"""MI355X: the ESP kernel (dragonfly/gp/kernel.py:671-744; DFH_KERNEL_ESP, csrc/kernmat.hip kernmat_esp_kernel) on the
+"""MI355X: the ESP kernel (dragonfly/gp/kernel.py:671-744; DFH_KERNEL_ESP, csrc/km_esp.hip kernmat_esp_kernel) on the
 device, against the REAL reference's outputs (tests/golden/esp_*.npz, tools/make_esp_golden.py).
 
 Numerics: the reference's Newton-Girard recursion cancels as the order approaches d.  Where the order is at most

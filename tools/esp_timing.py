@@ -1,4 +1,4 @@
-"""Times the ESP kernel (DFH_KERNEL_ESP, csrc/kernmat.hip kernmat_esp_kernel) on the device and prints one JSON object:
+"""Times the ESP kernel (DFH_KERNEL_ESP, csrc/km_esp.hip kernmat_esp_kernel) on the device and prints one JSON object:
 the symmetric Gram matrix at three (n, d, order) against the fp64 VALU roofline, a cross matrix, a fit plus an EI
 arg-max over 65536 candidates, and a 64-candidate tuning batch.
 
