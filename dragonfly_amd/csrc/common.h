@@ -60,6 +60,14 @@ constexpr int CHOL_MAX_BATCH = 64;
 // function attributes (dynamic LDS limits) are per device: the "already set" flags are indexed by it
 constexpr int DFH_MAX_DEVICES = 64;
 
+// The labels of the last tuning call, kept on the device between calls: the host copy a call's labels are compared with,
+// the device copy (scratch slot SCR_YCACHE), sum y and sum y^2
+struct LabelCache {
+  std::vector<double> host;
+  const double* dev = nullptr;
+  double sum = 0.0, sum2 = 0.0;
+};
+
 struct dfh_ctx {
   int device = 0;
   hipStream_t stream = nullptr;      // every kernel is launched on this stream ...
@@ -74,10 +82,7 @@ struct dfh_ctx {
   // the time-out of ~1 s on every fit
   int64_t chol_fallbacks = 0;
   int chol_fallback_streak = 0, chol_cooldown = 0;
-  // labels of the last tuning call, resident (lml_batch_wg): host copy to compare with, device copy, sum y and sum y^2
-  std::vector<double> ycache_host;
-  const double* ycache_dev = nullptr;
-  double ycache_sum = 0.0, ycache_sum2 = 0.0;
+  LabelCache labels;               // labels of the last tuning call, resident (lml.hip: resident_labels)
   int lml_team_cooldown = 0;       // tuning batches that take one workgroup per candidate after a team's hand-off timed out
   hipEvent_t ev0 = nullptr, ev1 = nullptr;         // dfh_timer_begin / end
   // scratch pool: grow-only named slots reused across calls (no hipMalloc in hot loops)
@@ -296,35 +301,6 @@ int kerndev_stage_many(KernDev* kds, int count, char* host, void* d_blob, size_t
 size_t kerndev_blob_bytes(const KernDev& kd);
 void kerndev_blob_fill(const KernDev& kd, char* host);     // the image itself, kerndev_blob_bytes(kd) bytes at host
 int kerndev_upload_many(dfh_ctx* ctx, KernDev* kds, int count, void* d_blob, size_t blob_bytes);
-// One-launch tuning objective for small problems (lml_tiny.hip: k_lml_tiny): applies when
-// n <= TINY_MAX_N and every candidate's packed width / part count fits the LDS budget.
-constexpr int64_t TINY_MAX_N = 128;
-constexpr int64_t TINY64_MAX_N = 63;      // k_lml_tiny64: the system (n + 1 rows) is one 64 x 64 tile
-constexpr int TINY_MAX_P = 64, TINY_MAX_PARTS = 16;
-bool lml_tiny_applies(const KernDev* kds, int count, int64_t n);
-// The blob of a small-problem tuning call in the context's pinned (mapped, coherent) buffer:
-// TinyCand[count] | kernel images | y[n] | 10^-11 .. 10^4 | (64-byte aligned) results [count][4]
-struct TinyBlob {
-  char* host = nullptr; size_t bytes = 0, y_off = 0, pow_off = 0;
-  double* res = nullptr;
-  int Pmax = 1, parts_max = 1;
-};
-int tiny_blob_build(dfh_ctx* ctx, const KernDev* kds, int count, int64_t n, const double* y_host,
-                    const double* noise_vars, const double* mean_consts, TinyBlob* tb);
-int tiny_poll_results(dfh_ctx* ctx, volatile double* vres, int count, const char* what);
-// TINY64_MAX_N < n <= LMLF_MAX_N, a handful of candidates: Gram matrix, factorisation and forward solve of each candidate in ONE
-// launch by one workgroup (lml_wg.h: lml_wgf_kernel), descriptors and results through the pinned buffer.
-// info[c]: 0 = logdet_dot[2c], [2c+1] are valid; otherwise the candidate is for the lock-step schedule (a failed pivot:
-// the ladder; no noise: nothing bounds the augmented pivot).
-constexpr int64_t LMLF_MAX_N = 128;     // (beyond, the team schedule -- one copy up, one memset, one copy back per group since round 6 -- is as fast: 101 us
-                                         //  at n = 129 .. 191 against the one workgroup's 105 .. 143; the kernel itself is tested up to n = 255 through DFH_LML_FUSED_MAX_N)
-bool lml_wg_fused_applies(const KernDev* kds, int count, int64_t n);
-int lml_wg_fused_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double* dX, int64_t n, int64_t ldx,
-                       const double* y_host, const double* noise_vars, const double* mean_consts,
-                       double* logdet_dot, long long* info);
-int lml_tiny_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double* dX, int64_t n, int64_t ldx,
-                   const double* y_host, const double* noise_vars, const double* mean_consts,
-                   bool allow_jitter, double* logdet_dot, int32_t* powers);
 int kerndev_build_dist(dfh_ctx* ctx, int dim, KernDev* out);
 int kerndev_clone(dfh_ctx* ctx, const KernDev& src, KernDev* out);   // deep copy with its own device image
 void kerndev_free(KernDev* kd);
@@ -393,16 +369,8 @@ int stable_cholesky_device(dfh_ctx* ctx, double* A, int64_t n, double* keep_inv,
 constexpr int DFH_INTERNAL_RETRY = 1000;   // chol.hip internal: never crosses the C-ABI (a hand-off wait expired)
 constexpr int DFH_INTERNAL_RETRY_COND = 1001;   // ... a block inverse too poor for the inverse-based panel solve (deterministic)
 
-// The tuning objective of `count` candidates, one workgroup per candidate (lml_wg.h: lml_wg_kernel): Cholesky of the
-// augmented matrix [[K, .], [(y - m)^T, c]] of each, sum(log L_ii) and |L^-1 (y - m)|^2 out.  K: matrices padded to
-// order 64 * ceil((n + 1) / 64) (only the n x n part has to be filled), sK doubles apart, row stride ld.
+// the largest n the tuning objective runs with one workgroup (or a team) per candidate (lml.h; mgpu.hip shards by it)
 constexpr int64_t LMLWG_MAX_N = 2047;
-// team > 1: that many workgroups per candidate (for groups far smaller than the device); *d_status != 0 afterwards
-// means a hand-off between them timed out and the launch's results are void (repeat with team = 1).
-int lml_wg_batch(dfh_ctx* ctx, double* K, int64_t sK, int64_t ld, int64_t n, int count, const double* d_y,
-                 const double* d_par, double* d_out2, long long* d_info, int team = 1,
-                 unsigned long long* d_status = nullptr, int* d_sync_zeroed = nullptr);
-constexpr int LMLT_SYNC_INTS = 64;     // flags of a team, per candidate (lml_wg.h: diag[j], then brow[j]); a caller that passes d_sync_zeroed sizes it with this
 
 // alpha-solves with the factor and its diagonal-block inverses (in place on x[n]):
 //   forward : x <- L^{-1} x          backward : x <- L^{-T} x

@@ -1,6 +1,6 @@
-// The tuning objective, extern "C" dfh_gp_lml_batch: its dispatcher, the workgroup-per-candidate and lock-step schedules,
+// The tuning objective, extern "C" dfh_gp_lml_batch: its route chooser, the workgroup-per-candidate and lock-step schedules,
 // and the kernels of the lock-step schedule's solve stage (the one-launch forms live in lml_tiny.hip and lml_wg.h).
-#include "common.h"
+#include "lml.h"
 #include <cstring>
 #include <math.h>
 #include <algorithm>
@@ -84,58 +84,11 @@ __global__ __launch_bounds__(256) void k_logdet_sumsq_batch(const double* __rest
   if (threadIdx.x == 0) { out[2 * blockIdx.x] = s1[0]; out[2 * blockIdx.x + 1] = s2[0]; }
 }
 
-// n <= CHOL_NB (one diagonal block): the whole solve stage of a candidate in one workgroup --
-// yc = y - m, z = L^-1 yc through the explicit block inverse M (followed by steps[c] steps of
-// iterative refinement against the clean copy Ld of the block, chol.hip: refine_steps), then
-// out = {sum log L_ii, z . z}  (= yc . alpha: the backward solve is not needed).  blockIdx.x = candidate.
-__global__ __launch_bounds__(256) void k_lml_finish_small(const double* __restrict__ inv, long sInv,
-                                                          const double* __restrict__ y,
-                                                          const double* __restrict__ means, int n,
-                                                          const int* __restrict__ steps,
-                                                          double* __restrict__ out2) {
-  __shared__ double yc[CHOL_NB], z[CHOL_NB], r[CHOL_NB], red[8];
-  const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  inv += (long)c * sInv;
-  const double* Ld = inv + CHOL_NB * CHOL_NB;                // clean copy of the factor (one block: nblk = 1)
-  const double mean = means[c];
-  const int nsteps = steps[c];
-  for (int i = tid; i < n; i += 256) yc[i] = y[i] - mean;
-  __syncthreads();
-  // dst_i (+)= sum_{j <= i} A[i][j] src[j], a wave per row
-  auto lower_mv = [&](const double* A, const double* src, double* dst, double sign, const double* base) {
-    for (int i = wave; i < n; i += 4) {
-      const double* row = A + (long)i * CHOL_NB;
-      double s = 0.0;
-      for (int j = lane; j <= i; j += 64) s = fma(row[j], src[j], s);
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-      if (lane == 0) dst[i] = (base ? base[i] : 0.0) + sign * s;
-    }
-    __syncthreads();
-  };
-  lower_mv(inv, yc, z, 1.0, nullptr);                       // z = M yc
-  for (int s = 0; s < nsteps; ++s) {
-    lower_mv(Ld, z, r, -1.0, yc);                           // r = yc - L z
-    lower_mv(inv, r, z, 1.0, z);                            // z += M r
-  }
-  // (y - m)^T alpha = ||L^-1 (y - m)||^2 = z . z: the backward solve is not needed for the likelihood
-  double ld = 0.0, dt = 0.0;
-  for (int j = tid; j < n; j += 256) {
-    dt = fma(z[j], z[j], dt);
-    ld += log(Ld[(long)j * CHOL_NB + j]);
-  }
-  for (int off = 32; off > 0; off >>= 1) { ld += __shfl_down(ld, off, 64); dt += __shfl_down(dt, off, 64); }
-  if (lane == 0) { red[wave] = ld; red[4 + wave] = dt; }
-  __syncthreads();
-  if (tid == 0) {
-    out2[2 * c] = (red[0] + red[1]) + (red[2] + red[3]);
-    out2[2 * c + 1] = (red[4] + red[5]) + (red[6] + red[7]);
-  }
-}
-
-// The same stage without the 512-block inverse: forward substitution over 64-blocks with the factor
-// itself and the inverses of its 64 x 64 diagonal blocks (what trtri64_kernel leaves on the diagonal
-// of the inverse buffer) -- z_b = Linv_bb (r_b - sum_{i<b} L_bi z_i).  Saves the inverse assembly
-// (six GEMM launches) and its quality measurement per call; a 64-block inverse needs no refinement.
+// n <= CHOL_NB (one diagonal block): the whole solve stage of a candidate in one workgroup, without the 512-block
+// inverse -- r = y - m, forward substitution over 64-blocks with the factor itself and the inverses of its 64 x 64
+// diagonal blocks (what trtri64_kernel leaves on the diagonal of the inverse buffer), z_b = Linv_bb (r_b - sum_{i<b} L_bi z_i),
+// then out = {sum log L_ii, z . z}  (= yc . alpha: the backward solve is not needed).  blockIdx.x = candidate.  Saves the
+// inverse assembly (six GEMM launches) and its quality measurement per call; a 64-block inverse needs no refinement.
 __global__ __launch_bounds__(256) void k_lml_finish_small64(const double* __restrict__ L, long sL, long ldl,
                                                             const double* __restrict__ inv, long sInv,
                                                             const double* __restrict__ y,
@@ -184,17 +137,51 @@ __global__ __launch_bounds__(256) void k_lml_finish_small64(const double* __rest
 
 namespace {
 
-// the switches that more than one place consults, read when the library is loaded
-const bool small64_on = env_flag("DFH_LML_SMALL64", true);     // n <= 512: substitution with 64-block inverses, no 512-block inverse
-const double group_gib_env = env_double("DFH_LML_GROUP_GIB", 8.0);
-const double group_gib = group_gib_env > 0.0 ? group_gib_env : 8.0;   // Gram matrices of one group of candidates
-
-// the arguments of dfh_gp_lml_batch, X resolved to the device; cand_base: index of descs[0] in the caller's list (error messages)
-struct LmlCall {
-  dfh_ctx* ctx; const dfh_kernel_desc* descs; int32_t nb; const double* dX; int64_t n, d; const double* y;
-  const double* mean_consts; const double* noise_vars; int flags; double* lml_out; int32_t* jitter_powers;
-  int cand_base;
+// The DFH_LML_* switches of the route chooser and the two schedules, read once per process at the
+// first call.  A launcher's own switches stay beside it: DFH_LML_DIRECT, DFH_LML_TINY64 (lml_tiny.hip), DFH_LML_FUSED,
+// DFH_LML_FUSED_MAX_N (lml_wg.h: lml_fused_limits).
+struct LmlSwitches {
+  bool tiny = env_flag("DFH_LML_TINY", true);                 // the one-launch forms
+  bool wg = env_flag("DFH_LML_WG", true);                     // one workgroup (or team) per candidate; 0: lock-step for every n
+  int wg_min_batch = env_int("DFH_LML_WG_MIN_BATCH", 1);      // ... for calls of at least this many candidates
+  int wg_group = env_int("DFH_LML_WG_GROUP", 0);              // > 0: candidates per group of that route (default: one per CU)
+  int team = env_int("DFH_LML_TEAM", -1);                     // 0 = never a team, N = teams of up to N workgroups (default: up to 8)
+  double group_gib = env_double("DFH_LML_GROUP_GIB", 8.0);    // Gram matrices of one group of candidates (<= 0: the default)
+  bool batch_solve = env_flag("DFH_LML_BATCH_SOLVE", true);   // lock-step solve stage at n > 512: all candidates per launch
 };
+const LmlSwitches& lml_switches() {
+  static const LmlSwitches sw;
+  return sw;
+}
+
+// how many matrices of `doubles` elements a group may hold (DFH_LML_GROUP_GIB)
+int64_t group_cap_by_memory(int64_t doubles) {
+  const double gib = lml_switches().group_gib > 0.0 ? lml_switches().group_gib : 8.0;
+  return std::max<int64_t>(1, (int64_t)(gib * 1073741824.0 / ((double)doubles * 8.0)));
+}
+
+// The one place that knows a threshold: which way a call goes.
+//   PsdEach  a PSD flag: a projection is per matrix, every candidate is a fit of its own
+//   Fused    a handful of mid-sized candidates (a slice sampler's call at 64 <= n <= 128): Gram matrix, factorisation and
+//            forward solve of each in ONE launch by one workgroup, nothing copied (lml_wg.h: lml_wgf_kernel)
+//   Tiny     small problems: pack, Gram matrix, stable_cholesky and the solve of every candidate in ONE launch (lml_tiny.hip)
+//   Wg       one workgroup or a team per candidate up to n = LMLWG_MAX_N
+//   Lockstep groups through the batched cholesky_device, any n
+enum class LmlRoute { PsdEach, Fused, Tiny, Wg, Lockstep };
+
+LmlRoute lml_route(const LmlCall& a) {
+  const LmlSwitches& sw = lml_switches();
+  if (a.flags & DFH_FIT_PSD_FLAGS) return LmlRoute::PsdEach;
+  if (sw.tiny && a.n <= std::max(TINY_MAX_N, LMLF_KERNEL_MAX_N) && lml_one_launch_kernels(a.kds, a.nb)) {
+    const LmlFusedLimits fused = lml_fused_limits();          // (DFH_LML_FUSED_MAX_N is capped at what the kernel takes)
+    if (a.n > TINY64_MAX_N && a.n <= std::min(fused.max_n, LMLF_KERNEL_MAX_N) && a.nb <= fused.max_count &&
+        lml_fused_fits_lds(a.kds, a.nb, a.n))
+      return LmlRoute::Fused;
+    if (a.n <= TINY_MAX_N) return LmlRoute::Tiny;
+  }
+  if (sw.wg && a.n <= LMLWG_MAX_N && a.nb >= sw.wg_min_batch) return LmlRoute::Wg;
+  return LmlRoute::Lockstep;
+}
 
 // *y_host <- y where the host can read it: y itself, or a copy in `hold` when the labels are resident on the device
 int labels_on_host(dfh_ctx* ctx, const double* y, int64_t n, int flags, std::vector<double>& hold, const double** y_host) {
@@ -214,24 +201,22 @@ struct GroupShape {
   bool uniform = true;                       // structurally identical single-part kernels
 };
 
-// kds[0..g) <- the host descriptors of descs[c0..c0+g)
-int stage_group(const dfh_kernel_desc* descs, int c0, int g, std::vector<KernDev>& kds, GroupShape& gs) {
-  gs = GroupShape();
+// of the g candidates kds[0..g), a slice of the call's descriptors
+GroupShape group_shape(const KernDev* kds, int g) {
+  GroupShape gs;
   for (int c = 0; c < g; ++c) {
-    kds[c] = KernDev();
-    DFH_TRY(kerndev_build_host(&descs[c0 + c], &kds[c]));
     gs.Pmax = std::max<int64_t>(gs.Pmax, kds[c].P);
     gs.parts_max = std::max<int64_t>(gs.parts_max, kds[c].n_parts);
     gs.blob_bytes += kerndev_blob_bytes(kds[c]);
     gs.uniform = gs.uniform && !kds[c].multi && kds[c].n_parts == 1 && kds[c].P == kds[0].P &&
                  kerndev_blob_bytes(kds[c]) == kerndev_blob_bytes(kds[0]);
   }
-  return DFH_OK;
+  return gs;
 }
 
 // K + noise_var * I (gp_core.py:843) of the g staged candidates, candidate c at K + c * sK with row stride ldK: a uniform
 // group in one pack and one Gram launch (noise d_noise[c], on the device), otherwise candidate by candidate (h_noise[c])
-int build_group_grams(dfh_ctx* ctx, const std::vector<KernDev>& kds, int g, const GroupShape& gs, const double* dX,
+int build_group_grams(dfh_ctx* ctx, const KernDev* kds, int g, const GroupShape& gs, const double* dX,
                       int64_t n, int64_t d, double* Xpb, double* Npb, const double* d_noise, const double* h_noise,
                       double* K, int64_t sK, int64_t ldK) {
   const int64_t sXp = n * gs.Pmax, sNp = n * gs.parts_max;
@@ -248,138 +233,182 @@ int build_group_grams(dfh_ctx* ctx, const std::vector<KernDev>& kds, int g, cons
   return DFH_OK;
 }
 
-// The lock-step schedule: groups of up to CHOL_MAX_BATCH candidates through the batched cholesky_device (any n)
+// ---- the lock-step schedule: groups of up to CHOL_MAX_BATCH candidates through the batched cholesky_device (any n) ----
+
+// the buffers of a call's groups (scratch slots of the context: nothing to free) and their host mirrors, for G candidates
+struct LockstepBufs {
+  int64_t n, nblk, ldK, strideK, strideInv;
+  const double* dy = nullptr;
+  double *Kb = nullptr, *invb = nullptr, *vecs = nullptr, *red = nullptr, *dpar = nullptr;   // dpar: [g] noise, then [g] mean
+  std::vector<double> hred, hpar;
+  std::vector<int> refine;                   // refinement steps per candidate and diagonal block
+  explicit LockstepBufs(int64_t n_)
+      : n(n_), nblk((n_ + CHOL_NB - 1) / CHOL_NB), ldK((n_ + 1) & ~(int64_t)1),     // even leading dimension: 16-byte row starts
+        strideK(n_ * ldK), strideInv(inv_buffer_doubles(n_)) {}
+};
+// candidates c0 .. c0 + g of the call, their descriptors uploaded and their inputs packed at Xpb / Npb
+struct LockstepGroup { int c0, g; const KernDev* kds; GroupShape gs; double *Xpb, *Npb; };
+
+int lockstep_buffers(const LmlCall& a, int G, LockstepBufs& b) {
+  dfh_ctx* ctx = a.ctx;
+  DFH_TRY(to_device(ctx, a.y, (size_t)b.n * 8, SCR_STAGE_B, &b.dy));
+  DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)G * b.strideK * 8, (void**)&b.Kb));
+  DFH_TRY(scratch_get(ctx, SCR_TSK, (size_t)G * b.strideInv * 8, (void**)&b.invb));
+  DFH_TRY(scratch_get(ctx, SCR_VEC, (size_t)G * b.n * 8 * 2, (void**)&b.vecs));
+  DFH_TRY(scratch_get(ctx, SCR_OUT2, (size_t)std::max(256, G * 16), (void**)&b.red));   // SCR_RED belongs to the gemv partials
+  DFH_TRY(scratch_get(ctx, SCR_OUT, (size_t)std::max(256, G * 16), (void**)&b.dpar));
+  b.hred.resize((size_t)G * 2); b.hpar.resize((size_t)G * 2);
+  b.refine.assign((size_t)G * b.nblk, 0);
+  return DFH_OK;
+}
+
+// descriptors (device images in one scratch blob: nothing to free), room for the packed inputs, {noise, mean} of the group
+int lockstep_stage_group(const LmlCall& a, LockstepBufs& b, int c0, int g, LockstepGroup& grp) {
+  dfh_ctx* ctx = a.ctx;
+  grp = LockstepGroup{c0, g, a.kds + c0, group_shape(a.kds + c0, g), nullptr, nullptr};
+  void* blob = nullptr;
+  DFH_TRY(scratch_get(ctx, SCR_AUG2, grp.gs.blob_bytes, &blob));
+  DFH_TRY(kerndev_upload_many(ctx, a.kds + c0, g, blob, grp.gs.blob_bytes));
+  DFH_TRY(scratch_get(ctx, SCR_XS, (size_t)g * b.n * grp.gs.Pmax * 8, (void**)&grp.Xpb));
+  DFH_TRY(scratch_get(ctx, SCR_XS2, (size_t)g * b.n * grp.gs.parts_max * 8, (void**)&grp.Npb));
+  for (int c = 0; c < g; ++c) {
+    b.hpar[c] = a.noise_vars[c0 + c];
+    b.hpar[g + c] = a.mean_consts ? a.mean_consts[c0 + c] : 0.0;
+  }
+  DFH_HIP(hipMemcpyAsync(b.dpar, b.hpar.data(), (size_t)g * 16, hipMemcpyHostToDevice, ctx->stream));
+  return DFH_OK;
+}
+
+// K + noise_var * I of candidate c again, from the packed inputs (a failed factorisation destroys it)
+int lockstep_rebuild(const LmlCall& a, const LockstepBufs& b, const LockstepGroup& grp, int c) {
+  const int64_t n = b.n;
+  double* Xp = grp.Xpb + c * n * grp.gs.Pmax; double* Np = grp.Npb + c * n * grp.gs.parts_max;
+  return kernmat_gram(a.ctx, grp.kds[c], 0, grp.kds[c].n_parts, true, KmPts{Xp, Np, n}, a.noise_vars[grp.c0 + c],
+                      b.Kb + c * b.strideK, b.ldK);
+}
+
+// the batched factorisation; a candidate whose matrix is not positive definite then takes the stable_cholesky ladder on
+// its own, exactly as a single fit would
+int lockstep_factor_group(const LmlCall& a, LockstepBufs& b, const LockstepGroup& grp) {
+  dfh_ctx* ctx = a.ctx;
+  const int64_t n = b.n;
+  int64_t piv[CHOL_MAX_BATCH] = {0};
+  // n <= 512: the finish kernel substitutes with 64-blocks, so the 512-block inverse is not built
+  const bool inv64_only = n <= CHOL_NB;
+  const std::function<int()> rebuild_all = [&]() -> int {
+    for (int c = 0; c < grp.g; ++c) DFH_TRY(lockstep_rebuild(a, b, grp, c));
+    return DFH_OK;
+  };
+  int rc = cholesky_device(ctx, b.Kb, n, b.ldK, b.invb, piv, grp.g, b.strideK, b.strideInv, b.refine.data(), inv64_only,
+                           &rebuild_all);
+  if (rc != DFH_OK && rc != DFH_ERR_NOT_PD) return rc;
+  for (int c = 0; c < grp.g; ++c) {
+    const int cand = grp.c0 + c;
+    if (a.jitter_powers) a.jitter_powers[cand] = INT32_MIN;
+    if (piv[c] == 0) continue;
+    if (a.flags & DFH_FIT_NO_JITTER) {
+      dfh_set_error("Matrix is not positive definite (candidate %d, pivot %lld)", a.cand_base + cand, (long long)piv[c]);
+      return DFH_ERR_NOT_PD;
+    }
+    auto rebuild = [&]() -> int { return lockstep_rebuild(a, b, grp, c); };
+    DFH_TRY(rebuild());
+    int32_t jp = INT32_MIN;
+    DFH_TRY(stable_cholesky_device(ctx, b.Kb + c * b.strideK, n, b.invb + c * b.strideInv, true, rebuild, &jp, nullptr, b.ldK,
+                                   b.refine.data() + (size_t)c * b.nblk));
+    if (a.jitter_powers) a.jitter_powers[cand] = jp;
+  }
+  return DFH_OK;
+}
+
+// n <= 512, one workgroup per candidate: substitution with 64-blocks
+// (a candidate that went through the jitter ladder has the full inverse in its slot: its diagonal
+//  64-blocks are the inverses of the factor's diagonal blocks all the same)
+int lockstep_solve_small64(dfh_ctx* ctx, const LockstepBufs& b, int g) {
+  hipLaunchKernelGGL(k_lml_finish_small64, dim3((unsigned)g), dim3(256), 0, ctx->stream, b.Kb, (long)b.strideK, (long)b.ldK,
+                     b.invb, (long)b.strideInv, b.dy, b.dpar + g, (int)b.n, b.red);
+  DFH_LAUNCH_CHECK();
+  return DFH_OK;
+}
+
+// all candidates per launch: r = y - m; for each 512-block z_b = M_b r_b, r_below -= L[below, b] z_b
+int lockstep_solve_batched(dfh_ctx* ctx, const LockstepBufs& b, int g) {
+  const int64_t n = b.n, NB = CHOL_NB;
+  const long sv = 2 * (long)n;                 // candidate c: r at vecs + c*sv, z behind it
+  double* vecs = b.vecs;
+  hipLaunchKernelGGL(k_centre_batch, dim3((unsigned)((n + 255) / 256), (unsigned)g), dim3(256), 0, ctx->stream, b.dy,
+                     b.dpar + g, vecs, (long)n);
+  DFH_LAUNCH_CHECK();
+  for (int64_t b0 = 0; b0 < n; b0 += NB) {
+    const int64_t w = std::min<int64_t>(NB, n - b0), below = n - b0 - w;
+    hipLaunchKernelGGL(k_gemv_rows_wave_batch, dim3((unsigned)((w + 3) / 4), (unsigned)g), dim3(256), 0, ctx->stream,
+                       b.invb + (b0 / NB) * NB * NB, (long)b.strideInv, (long)w, (long)w, (long)NB, vecs + b0, sv, 1.0,
+                       (const double*)nullptr, 0.0, vecs + n + b0, sv);
+    DFH_LAUNCH_CHECK();
+    if (below > 0) {
+      hipLaunchKernelGGL(k_gemv_rows_wave_batch, dim3((unsigned)((below + 3) / 4), (unsigned)g), dim3(256), 0,
+                         ctx->stream, b.Kb + (b0 + w) * b.ldK + b0, (long)b.strideK, (long)below, (long)w, (long)b.ldK,
+                         vecs + n + b0, sv, -1.0, vecs + b0 + w, 1.0, vecs + b0 + w, sv);
+      DFH_LAUNCH_CHECK();
+    }
+  }
+  hipLaunchKernelGGL(k_logdet_sumsq_batch, dim3((unsigned)g), dim3(256), 0, ctx->stream, b.Kb, (long)b.strideK, (long)n,
+                     (long)b.ldK, vecs + n, sv, b.red);
+  DFH_LAUNCH_CHECK();
+  return DFH_OK;
+}
+
+// candidate by candidate (some block's inverse wants refinement, or DFH_LML_BATCH_SOLVE=0)
+int lockstep_solve_each(dfh_ctx* ctx, const LockstepBufs& b, int g) {
+  const int64_t n = b.n;
+  for (int c = 0; c < g; ++c) {
+    double* yc = b.vecs + (int64_t)c * 2 * n;
+    double* alpha = yc + n;
+    hipLaunchKernelGGL(k_centre, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, b.dy, b.hpar[g + c], yc, alpha, (long)n);
+    DFH_LAUNCH_CHECK();
+    // alpha = L^T \ (L \ (y - m))      (gp_core.py:161-163)
+    DFH_TRY(trsv_both(ctx, b.Kb + c * b.strideK, n, b.ldK, b.invb + c * b.strideInv, alpha, b.refine.data() + (size_t)c * b.nblk));
+    DFH_TRY(logdet_and_dot_device(ctx, b.Kb + c * b.strideK, n, b.ldK, yc, alpha, b.red + 2 * c));
+  }
+  return DFH_OK;
+}
+
+// the solve stage in the form the size and the inverses' quality allow, and the group's results
+int lockstep_solve_group(const LmlCall& a, LockstepBufs& b, const LockstepGroup& grp) {
+  dfh_ctx* ctx = a.ctx;
+  const int g = grp.g;
+  bool any_refine = false;
+  for (size_t i = 0; i < (size_t)g * b.nblk; ++i) any_refine = any_refine || b.refine[i] > 0;
+  if (b.n <= CHOL_NB) DFH_TRY(lockstep_solve_small64(ctx, b, g));
+  else if (!any_refine && lml_switches().batch_solve) DFH_TRY(lockstep_solve_batched(ctx, b, g));
+  else DFH_TRY(lockstep_solve_each(ctx, b, g));
+  DFH_HIP(hipMemcpyAsync(b.hred.data(), b.red, (size_t)g * 16, hipMemcpyDeviceToHost, ctx->stream));
+  DFH_HIP(hipStreamSynchronize(ctx->stream));
+  for (int c = 0; c < g; ++c) a.lml_out[grp.c0 + c] = lml_value(b.hred[2 * c], b.hred[2 * c + 1], b.n);
+  return DFH_OK;
+}
+
 int lml_batch_lockstep(const LmlCall& a) {
   dfh_ctx* ctx = a.ctx;
-  const int32_t nb = a.nb;
-  const int64_t n = a.n, NB = CHOL_NB;
-  const int64_t nblk = (n + NB - 1) / NB;
-  const int64_t ldK = (n + 1) & ~(int64_t)1;                 // even leading dimension: 16-byte row starts
-  const int64_t strideK = n * ldK, strideInv = inv_buffer_doubles(n);
+  LockstepBufs b(a.n);
   // group size: up to CHOL_MAX_BATCH matrices and (DFH_LML_GROUP_GIB, default 8) GiB of Gram
   // matrices at a time.  Measured ms per candidate at 2 / 8 GiB: n=4096 1.55 / 1.07, n=16384
   // 42.6 (one at a time) / 30.0 (four in lock-step: the panel chains of the four interleave).
-  const int64_t by_mem = std::max<int64_t>(1, (int64_t)(group_gib * 1073741824.0 / ((double)strideK * 8.0)));
-  const int G = (int)std::min<int64_t>(std::min<int64_t>(nb, CHOL_MAX_BATCH), by_mem);
-  std::vector<KernDev> kds((size_t)G);       // device images live in one scratch blob: nothing to free
-  const double* dy = nullptr;
-  DFH_TRY(to_device(ctx, a.y, (size_t)n * 8, SCR_STAGE_B, &dy));
-  double *Kb = nullptr, *invb = nullptr, *vecs = nullptr, *red = nullptr, *dpar = nullptr;
-  DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)G * strideK * 8, (void**)&Kb));
-  DFH_TRY(scratch_get(ctx, SCR_TSK, (size_t)G * strideInv * 8, (void**)&invb));
-  DFH_TRY(scratch_get(ctx, SCR_VEC, (size_t)G * n * 8 * 2, (void**)&vecs));
-  DFH_TRY(scratch_get(ctx, SCR_OUT2, (size_t)std::max(256, G * 16), (void**)&red));   // SCR_RED belongs to the gemv partials
-  DFH_TRY(scratch_get(ctx, SCR_OUT, (size_t)std::max(256, G * 24), (void**)&dpar));   // per candidate {noise, mean}, then int steps
-  std::vector<double> hred((size_t)G * 2), hpar((size_t)G * 2);
-  std::vector<int> refine((size_t)G * nblk, 0);           // refinement steps per candidate and diagonal block
-  for (int c0 = 0; c0 < nb; c0 += G) {
-    const int g = std::min(G, nb - c0);
-    GroupShape gs;
-    DFH_TRY(stage_group(a.descs, c0, g, kds, gs));
-    void* blob = nullptr;
-    DFH_TRY(scratch_get(ctx, SCR_AUG2, gs.blob_bytes, &blob));
-    DFH_TRY(kerndev_upload_many(ctx, kds.data(), g, blob, gs.blob_bytes));
-    double *Xpb = nullptr, *Npb = nullptr;
-    DFH_TRY(scratch_get(ctx, SCR_XS, (size_t)g * n * gs.Pmax * 8, (void**)&Xpb));
-    DFH_TRY(scratch_get(ctx, SCR_XS2, (size_t)g * n * gs.parts_max * 8, (void**)&Npb));
-    const int64_t sXp = n * gs.Pmax, sNp = n * gs.parts_max;
-    for (int c = 0; c < g; ++c) {
-      hpar[c] = a.noise_vars[c0 + c];
-      hpar[g + c] = a.mean_consts ? a.mean_consts[c0 + c] : 0.0;
-    }
-    DFH_HIP(hipMemcpyAsync(dpar, hpar.data(), (size_t)g * 16, hipMemcpyHostToDevice, ctx->stream));
-    auto build_M = [&](int c) -> int {           // K + noise_var * I again, from the packed inputs (a failed factorisation destroys it)
-      double* Xp = Xpb + c * sXp; double* Np = Npb + c * sNp;
-      return kernmat_gram(ctx, kds[c], 0, kds[c].n_parts, true, KmPts{Xp, Np, n}, a.noise_vars[c0 + c], Kb + c * strideK,
-                          ldK);
-    };
+  const int G = (int)std::min<int64_t>(std::min<int64_t>(a.nb, CHOL_MAX_BATCH), group_cap_by_memory(b.strideK));
+  DFH_TRY(lockstep_buffers(a, G, b));
+  for (int c0 = 0; c0 < a.nb; c0 += G) {
+    LockstepGroup grp;
+    DFH_TRY(lockstep_stage_group(a, b, c0, std::min(G, a.nb - c0), grp));
     {
       SectionTimer t(ctx, DFH_T_KERNMAT);
-      DFH_TRY(build_group_grams(ctx, kds, g, gs, a.dX, n, a.d, Xpb, Npb, dpar, a.noise_vars + c0, Kb, strideK, ldK));
+      DFH_TRY(build_group_grams(ctx, grp.kds, grp.g, grp.gs, a.dX, a.n, a.d, grp.Xpb, grp.Npb, b.dpar, a.noise_vars + c0, b.Kb,
+                                b.strideK, b.ldK));
     }
     {
       SectionTimer t(ctx, DFH_T_CHOL);
-      int64_t piv[CHOL_MAX_BATCH] = {0};
-      // n <= 512: the finish kernel substitutes with 64-blocks, so the 512-block inverse is not built
-      const bool inv64_only = small64_on && n <= NB;
-      const std::function<int()> rebuild_all = [&]() -> int {
-        for (int c = 0; c < g; ++c) DFH_TRY(build_M(c));
-        return DFH_OK;
-      };
-      int rc = cholesky_device(ctx, Kb, n, ldK, invb, piv, g, strideK, strideInv, refine.data(), inv64_only, &rebuild_all);
-      if (rc != DFH_OK && rc != DFH_ERR_NOT_PD) return rc;
-      for (int c = 0; c < g; ++c) {
-        if (a.jitter_powers) a.jitter_powers[c0 + c] = INT32_MIN;
-        if (piv[c] == 0) continue;
-        if (a.flags & DFH_FIT_NO_JITTER) {
-          dfh_set_error("Matrix is not positive definite (candidate %d, pivot %lld)", a.cand_base + c0 + c, (long long)piv[c]);
-          return DFH_ERR_NOT_PD;
-        }
-        auto rebuild = [&]() -> int { return build_M(c); };
-        DFH_TRY(rebuild());
-        int32_t jp = INT32_MIN;
-        DFH_TRY(stable_cholesky_device(ctx, Kb + c * strideK, n, invb + c * strideInv, true, rebuild, &jp, nullptr, ldK,
-                                       refine.data() + (size_t)c * nblk));
-        if (a.jitter_powers) a.jitter_powers[c0 + c] = jp;
-      }
+      DFH_TRY(lockstep_factor_group(a, b, grp));
     }
-    {
-      SectionTimer t(ctx, DFH_T_SOLVE);
-      if (n <= NB && small64_on) {
-        // (a candidate that went through the jitter ladder has the full inverse in its slot: its diagonal
-        //  64-blocks are the inverses of the factor's diagonal blocks all the same)
-        hipLaunchKernelGGL(k_lml_finish_small64, dim3((unsigned)g), dim3(256), 0, ctx->stream, Kb, (long)strideK, (long)ldK,
-                           invb, (long)strideInv, dy, dpar + g, (int)n, red);
-        DFH_LAUNCH_CHECK();
-      } else if (n <= NB) {
-        // one block per candidate (nblk = 1): its refinement steps ride behind {noise, mean} in dpar
-        int* dsteps = reinterpret_cast<int*>(dpar + 2 * g);
-        DFH_HIP(hipMemcpyAsync(dsteps, refine.data(), (size_t)g * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_lml_finish_small, dim3((unsigned)g), dim3(256), 0, ctx->stream, invb, (long)strideInv,
-                           dy, dpar + g, (int)n, dsteps, red);
-        DFH_LAUNCH_CHECK();
-      } else {
-        bool any_refine = false;
-        for (size_t i = 0; i < (size_t)g * nblk; ++i) any_refine = any_refine || refine[i] > 0;
-        static const bool batch_solve = env_flag("DFH_LML_BATCH_SOLVE", true);
-        if (!any_refine && batch_solve) {
-          // all candidates per launch: r = y - m; for each 512-block z_b = M_b r_b, r_below -= L[below, b] z_b
-          const long sv = 2 * (long)n;                 // candidate c: r at vecs + c*sv, z behind it
-          hipLaunchKernelGGL(k_centre_batch, dim3((unsigned)((n + 255) / 256), (unsigned)g), dim3(256), 0, ctx->stream, dy,
-                             dpar + g, vecs, (long)n);
-          DFH_LAUNCH_CHECK();
-          for (int64_t b0 = 0; b0 < n; b0 += NB) {
-            const int64_t w = std::min<int64_t>(NB, n - b0), below = n - b0 - w;
-            hipLaunchKernelGGL(k_gemv_rows_wave_batch, dim3((unsigned)((w + 3) / 4), (unsigned)g), dim3(256), 0, ctx->stream,
-                               invb + (b0 / NB) * NB * NB, (long)strideInv, (long)w, (long)w, (long)NB, vecs + b0, sv, 1.0,
-                               (const double*)nullptr, 0.0, vecs + n + b0, sv);
-            DFH_LAUNCH_CHECK();
-            if (below > 0) {
-              hipLaunchKernelGGL(k_gemv_rows_wave_batch, dim3((unsigned)((below + 3) / 4), (unsigned)g), dim3(256), 0,
-                                 ctx->stream, Kb + (b0 + w) * ldK + b0, (long)strideK, (long)below, (long)w, (long)ldK,
-                                 vecs + n + b0, sv, -1.0, vecs + b0 + w, 1.0, vecs + b0 + w, sv);
-              DFH_LAUNCH_CHECK();
-            }
-          }
-          hipLaunchKernelGGL(k_logdet_sumsq_batch, dim3((unsigned)g), dim3(256), 0, ctx->stream, Kb, (long)strideK, (long)n,
-                             (long)ldK, vecs + n, sv, red);
-          DFH_LAUNCH_CHECK();
-        } else {
-          for (int c = 0; c < g; ++c) {
-            double* yc = vecs + (int64_t)c * 2 * n;
-            double* alpha = yc + n;
-            hipLaunchKernelGGL(k_centre, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dy, hpar[g + c], yc, alpha, (long)n);
-            DFH_LAUNCH_CHECK();
-            // alpha = L^T \ (L \ (y - m))      (gp_core.py:161-163)
-            DFH_TRY(trsv_both(ctx, Kb + c * strideK, n, ldK, invb + c * strideInv, alpha, refine.data() + (size_t)c * nblk));
-            DFH_TRY(logdet_and_dot_device(ctx, Kb + c * strideK, n, ldK, yc, alpha, red + 2 * c));
-          }
-        }
-      }
-      DFH_HIP(hipMemcpyAsync(hred.data(), red, (size_t)g * 16, hipMemcpyDeviceToHost, ctx->stream));
-      DFH_HIP(hipStreamSynchronize(ctx->stream));
-      for (int c = 0; c < g; ++c) a.lml_out[c0 + c] = lml_value(hred[2 * c], hred[2 * c + 1], n);
-    }
+    SectionTimer t(ctx, DFH_T_SOLVE);
+    DFH_TRY(lockstep_solve_group(a, b, grp));
   }
   return DFH_OK;
 }
@@ -387,146 +416,246 @@ int lml_batch_lockstep(const LmlCall& a) {
 // candidate c of the call takes the lock-step schedule by itself (which runs the stable_cholesky ladder as a single fit would)
 int redo_alone(const LmlCall& a, int c) {
   LmlCall one = a;
-  one.descs += c; one.nb = 1; one.noise_vars += c; one.lml_out += c; one.cand_base += c;
+  one.descs += c; one.kds += c; one.nb = 1; one.noise_vars += c; one.lml_out += c; one.cand_base += c;
   if (one.mean_consts) one.mean_consts += c;
   if (one.jitter_powers) one.jitter_powers += c;
   return lml_batch_lockstep(one);
 }
 
-// One workgroup per candidate (lml_wg.h: lml_wg_kernel), 128 < n <= LMLWG_MAX_N: per group of up to one candidate
-// per CU three launches -- pack, Gram matrices, factor + forward solve + reductions -- and one copy back.  A
-// candidate whose matrix does not factor as it stands (or whose augmented pivot fails) is handed to the
-// lock-step schedule on its own, which runs the stable_cholesky ladder exactly as before.
-int lml_batch_wg(const LmlCall& a) {
-  dfh_ctx* ctx = a.ctx;
-  const int32_t nb = a.nb;
-  const int64_t n = a.n;
-  const double* y = a.y;
-  const int64_t nbt = (n + 1 + 63) / 64, NP = 64 * nbt, sK = NP * NP;
-  static const int group_env = env_int("DFH_LML_WG_GROUP", 0), group_max = group_env > 0 ? group_env : 0;
-  const int64_t by_mem = std::max<int64_t>(1, (int64_t)(group_gib * 1073741824.0 / ((double)sK * 8.0)));
-  const int64_t by_cu = group_max > 0 ? group_max : std::max(1, ctx->n_cu);
-  const int G = (int)std::min<int64_t>(std::min<int64_t>(nb, by_cu), by_mem);
-  // The labels stay resident between calls (round 6): a fitter asks thousands of times with the same y, and staging
-  // 16 KB of pageable memory per call -- copy, synchronise -- was a sixth of a small group's call.  Host labels are
-  // compared with the copy of the last call (memcmp: exact); device labels are used where they are.
-  const double* dy = nullptr;
-  double sum_y = 0.0, sum_y2 = 0.0;
+// ---- one workgroup (or a team) per candidate (lml_wg.h), n <= LMLWG_MAX_N: per group of up to one candidate per CU three
+// launches -- pack, Gram matrices, factor + forward solve + reductions -- and one copy back.  A candidate whose matrix
+// does not factor as it stands (or whose augmented pivot fails) is handed to the lock-step schedule on its own. ----
+
+// The labels stay resident between calls (round 6): a fitter asks thousands of times with the same y, and staging
+// 16 KB of pageable memory per call -- copy, synchronise -- was a sixth of a small group's call.  Host labels are
+// compared with the copy of the last call (memcmp: exact); device labels are used where they are.
+struct Labels { const double* dy; double sum_y, sum_y2; };
+
+int resident_labels(dfh_ctx* ctx, const double* y, int64_t n, int flags, Labels* out) {
   std::vector<double> y_hold;
   const double* y_host = nullptr;
-  DFH_TRY(labels_on_host(ctx, y, n, a.flags, y_hold, &y_host));
+  DFH_TRY(labels_on_host(ctx, y, n, flags, y_hold, &y_host));
   if (!y_hold.empty()) {                       // device labels, downloaded for their sums
-    dy = y;
-    for (int64_t i = 0; i < n; ++i) { sum_y += y_host[i]; sum_y2 = fma(y_host[i], y_host[i], sum_y2); }
-  } else {
-    double* ybuf = nullptr;
-    DFH_TRY(scratch_get(ctx, SCR_YCACHE, (size_t)std::max<int64_t>(2048, n) * 8, (void**)&ybuf));
-    if (ybuf != ctx->ycache_dev || ctx->ycache_host.size() != (size_t)n ||
-        std::memcmp(ctx->ycache_host.data(), y, (size_t)n * 8) != 0) {
-      ctx->ycache_host.assign(y, y + n);
-      DFH_HIP(hipMemcpyAsync(ybuf, ctx->ycache_host.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-      DFH_HIP(hipStreamSynchronize(ctx->stream));
-      ctx->ycache_dev = ybuf;
-      double s1 = 0.0, s2 = 0.0;
-      for (int64_t i = 0; i < n; ++i) { s1 += y[i]; s2 = fma(y[i], y[i], s2); }
-      ctx->ycache_sum = s1; ctx->ycache_sum2 = s2;
-    }
-    dy = ybuf;
-    sum_y = ctx->ycache_sum; sum_y2 = ctx->ycache_sum2;
+    *out = Labels{y, 0.0, 0.0};
+    for (int64_t i = 0; i < n; ++i) { out->sum_y += y_host[i]; out->sum_y2 = fma(y_host[i], y_host[i], out->sum_y2); }
+    return DFH_OK;
   }
-  // One control block per group on the device -- results [2 g] | failed pivots [g] | status [1] | team flags -- zeroed by
-  // ONE memset and copied back by ONE copy into the pinned buffer; descriptors and {aug. diagonal, mean, noise} go up
-  // from the pinned buffer in ONE copy.  (Round 5: three pageable copies up, three memsets, three pageable copies
-  // back and three synchronisations per group -- 160 of a small group's 210 us, profiles/r06_small_calls.txt.)
+  LabelCache& cache = ctx->labels;
+  double* ybuf = nullptr;
+  DFH_TRY(scratch_get(ctx, SCR_YCACHE, (size_t)std::max<int64_t>(2048, n) * 8, (void**)&ybuf));
+  if (ybuf != cache.dev || cache.host.size() != (size_t)n || std::memcmp(cache.host.data(), y, (size_t)n * 8) != 0) {
+    cache.host.assign(y, y + n);
+    DFH_HIP(hipMemcpyAsync(ybuf, cache.host.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    DFH_HIP(hipStreamSynchronize(ctx->stream));
+    cache.dev = ybuf;
+    cache.sum = cache.sum2 = 0.0;
+    for (int64_t i = 0; i < n; ++i) { cache.sum += y[i]; cache.sum2 = fma(y[i], y[i], cache.sum2); }
+  }
+  *out = Labels{ybuf, cache.sum, cache.sum2};
+  return DFH_OK;
+}
+
+// Where a group of g candidates keeps what.  One control block per group on the device, zeroed by ONE memset and copied
+// back by ONE copy into the pinned buffer; descriptors and {aug. diagonal, mean, noise} go up from the pinned buffer in
+// ONE copy.  (Round 5: three pageable copies up, three memsets, three pageable copies back and three synchronisations
+// per group -- 160 of a small group's 210 us, profiles/r06_small_calls.txt.)
+//   pinned:  descriptors | (16-byte aligned) {aug. diagonal, mean, noise} [3 g] | (64-byte aligned) what comes back [3 g + 1]
+//   control: results [2 g] | failed pivots [g] | status [1] | team flags [g][LMLT_SYNC_INTS]
+struct WgGroupLayout {
+  int g;
+  size_t up_par, up_bytes, back_off, back_bytes;
+  WgGroupLayout(int g_, size_t blob_bytes)
+      : g(g_), up_par((blob_bytes + 15) & ~size_t(15)), up_bytes(up_par + (size_t)g_ * 24),
+        back_off((up_bytes + 63) & ~size_t(63)), back_bytes((size_t)(3 * g_ + 1) * 8) {}
+  size_t pinned_bytes() const { return back_off + back_bytes; }
+  static size_t control_bytes(int G) { return (size_t)(3 * G + 8) * 8 + (size_t)G * LMLT_SYNC_INTS * sizeof(int); }
+  // failed pivots, status and a team's flags: one memset (the results in front of them are always written)
+  size_t zeroed_bytes(int team) const { return (size_t)(g + 1) * 8 + (team > 1 ? (size_t)g * LMLT_SYNC_INTS * sizeof(int) : 0); }
+  double* hpar(char* pinned) const { return reinterpret_cast<double*>(pinned + up_par); }
+  const double* hred(const char* pinned) const { return reinterpret_cast<const double*>(pinned + back_off); }
+  const long long* hinfo(const char* pinned) const { return reinterpret_cast<const long long*>(pinned + back_off) + 2 * g; }
+  unsigned long long hstatus(const char* pinned) const { return reinterpret_cast<const unsigned long long*>(pinned + back_off)[3 * g]; }
+  double* dpar(void* blob) const { return reinterpret_cast<double*>(static_cast<char*>(blob) + up_par); }
+  long long* dinfo(double* ctl) const { return reinterpret_cast<long long*>(ctl + 2 * g); }
+  unsigned long long* dstatus(double* ctl) const { return reinterpret_cast<unsigned long long*>(ctl + 3 * g); }
+  int* dsync(double* ctl) const { return reinterpret_cast<int*>(ctl + 3 * g + 1); }
+};
+
+// a call's buffers and the group in hand: candidates c0 .. c0 + g
+struct WgGroup {
+  int64_t nbt, NP, sK;                         // tile rows of the augmented system, padded order, doubles per matrix
+  Labels labels;
   double *Kb = nullptr, *ctl = nullptr;
-  DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)G * sK * 8, (void**)&Kb));
-  const size_t ctl_bytes = (size_t)(3 * G + 8) * 8 + (size_t)G * LMLT_SYNC_INTS * sizeof(int);
-  DFH_TRY(scratch_get(ctx, SCR_LMLCTL, ctl_bytes, (void**)&ctl));
-  std::vector<KernDev> kds((size_t)G);
-  std::vector<char> skip((size_t)G, 0);
-  // DFH_LML_TEAM: 0 = never a team, N = teams of up to N workgroups (default: up to 8)
-  static const int team_env = env_int("DFH_LML_TEAM", -1);
+  int c0 = 0, g = 0;
+  const KernDev* kds = nullptr;
+  GroupShape gs;
+  WgGroupLayout lay{0, 0};
+  char* pinned = nullptr;
+  void* blob = nullptr;
+  double *Xpb = nullptr, *Npb = nullptr;
+  std::vector<char> skip;                      // candidates that go to the lock-step schedule without being tried
+};
+
+// hpar <- {aug. diagonal, mean, noise} of the group; skip[c]: nothing bounds candidate c's augmented pivot
+void wg_fill_params(const LmlCall& a, WgGroup& w) {
+  const int g = w.g;
+  double* hpar = w.lay.hpar(w.pinned);
+  const double sum_y = w.labels.sum_y, sum_y2 = w.labels.sum_y2;
+  for (int c = 0; c < g; ++c) {
+    // the augmented row's diagonal entry: c = 1 + |y - m|^2 / s2 > z.z (the eigenvalues of K + s2 I are >= s2)
+    // (|y - m|^2 = sum y^2 - 2 m sum y + n m^2: a bound needs no more than that, with a hair of slack for its rounding)
+    const double m = a.mean_consts ? a.mean_consts[w.c0 + c] : 0.0, s2 = a.noise_vars[w.c0 + c];
+    const double r2 = std::max(0.0, (sum_y2 - 2.0 * m * sum_y + (double)a.n * m * m)) * (1.0 + 1e-6) + 1e-6 * sum_y2;
+    hpar[c] = 1.0 + r2 / s2;
+    hpar[g + c] = m;
+    hpar[2 * g + c] = s2;
+    // (no noise, or a ratio beyond the double range: nothing bounds z.z -- such a candidate takes the lock-step schedule)
+    w.skip[c] = !(s2 > 0.0) || !std::isfinite(hpar[c]);
+    if (w.skip[c]) hpar[c] = 1.0;
+  }
+}
+
+// a group that leaves most of the device idle gets a TEAM of workgroups per candidate (lml_wg.h: lml_team_kernel)
+// (a timed-out hand-off costs ~0.1 s of polling plus the rebuilt group, and a slice sampler calls a hundred thousand
+//  times: after one, the context's next 32 groups take one workgroup per candidate -- a shared device does not pay
+//  the stall on every call; advisor, round 5)
+int wg_pick_team(dfh_ctx* ctx, int g, int64_t nbt) {
+  const int team_env = lml_switches().team;
+  const bool team_cooling = ctx->lml_team_cooldown > 0;
+  if (team_cooling) --ctx->lml_team_cooldown;
+  int team = 1;
+  if (team_env != 0 && !team_cooling) {
+    const int cap = team_env > 0 ? team_env : 8;
+    while (team * 2 <= cap && (int64_t)team * 2 * g <= ctx->n_cu && team * 2 <= nbt) team *= 2;
+  }
+  return team;
+}
+
+// Gram matrices, the launch with `team` workgroups per candidate, and the control block back in the pinned buffer
+int wg_run_group(const LmlCall& a, const WgGroup& w, int team) {
+  dfh_ctx* ctx = a.ctx;
+  const int g = w.g;
+  double* dpar = w.lay.dpar(w.blob);
+  {
+    SectionTimer t(ctx, DFH_T_KERNMAT);
+    DFH_TRY(build_group_grams(ctx, w.kds, g, w.gs, a.dX, a.n, a.d, w.Xpb, w.Npb, dpar + 2 * g, a.noise_vars + w.c0, w.Kb, w.sK, w.NP));
+  }
+  {
+    SectionTimer t(ctx, DFH_T_CHOL);
+    DFH_HIP(hipMemsetAsync(w.lay.dinfo(w.ctl), 0, w.lay.zeroed_bytes(team), ctx->stream));
+    DFH_TRY(lml_wg_batch(ctx, w.Kb, w.sK, w.NP, a.n, g, w.labels.dy, dpar, w.ctl, w.lay.dinfo(w.ctl), team, w.lay.dstatus(w.ctl),
+                         w.lay.dsync(w.ctl)));
+  }
+  DFH_HIP(hipMemcpyAsync(w.pinned + w.lay.back_off, w.ctl, w.lay.back_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  DFH_HIP(hipStreamSynchronize(ctx->stream));
+  return DFH_OK;
+}
+
+// the group's results out; `redo` <- the candidates for the lock-step schedule
+void wg_collect(const LmlCall& a, const WgGroup& w, std::vector<int>& redo) {
+  const double* hred = w.lay.hred(w.pinned);
+  const long long* hinfo = w.lay.hinfo(w.pinned);
+  for (int c = 0; c < w.g; ++c) {
+    if (w.skip[c] || hinfo[c] != 0 || !std::isfinite(hred[2 * c]) || !std::isfinite(hred[2 * c + 1])) { redo.push_back(w.c0 + c); continue; }
+    if (a.jitter_powers) a.jitter_powers[w.c0 + c] = INT32_MIN;
+    a.lml_out[w.c0 + c] = lml_value(hred[2 * c], hred[2 * c + 1], a.n);
+  }
+}
+
+// descriptors and parameters of candidates c0 .. c0 + g staged in the pinned buffer and on their way up
+int wg_stage_group(const LmlCall& a, WgGroup& w, int c0, int g) {
+  dfh_ctx* ctx = a.ctx;
+  w.c0 = c0; w.g = g; w.kds = a.kds + c0;
+  w.gs = group_shape(w.kds, g);
+  w.lay = WgGroupLayout(g, w.gs.blob_bytes);
+  void* pinned = nullptr;
+  DFH_TRY(pinned_get(ctx, w.lay.pinned_bytes(), &pinned));
+  w.pinned = static_cast<char*>(pinned);
+  DFH_TRY(scratch_get(ctx, SCR_AUG2, w.lay.up_bytes, &w.blob));
+  DFH_TRY(kerndev_stage_many(a.kds + c0, g, w.pinned, w.blob, w.gs.blob_bytes));
+  DFH_TRY(scratch_get(ctx, SCR_XS, (size_t)g * a.n * w.gs.Pmax * 8, (void**)&w.Xpb));
+  DFH_TRY(scratch_get(ctx, SCR_XS2, (size_t)g * a.n * w.gs.parts_max * 8, (void**)&w.Npb));
+  wg_fill_params(a, w);
+  DFH_HIP(hipMemcpyAsync(w.blob, w.pinned, w.lay.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+  return DFH_OK;
+}
+
+int lml_batch_wg(const LmlCall& a) {
+  dfh_ctx* ctx = a.ctx;
+  WgGroup w;
+  w.nbt = (a.n + 1 + 63) / 64; w.NP = 64 * w.nbt; w.sK = w.NP * w.NP;
+  const int wg_group = lml_switches().wg_group;
+  const int64_t by_cu = wg_group > 0 ? wg_group : std::max(1, ctx->n_cu);
+  const int G = (int)std::min<int64_t>(std::min<int64_t>(a.nb, by_cu), group_cap_by_memory(w.sK));
+  DFH_TRY(resident_labels(ctx, a.y, a.n, a.flags, &w.labels));
+  DFH_TRY(scratch_get(ctx, SCR_KCT, (size_t)G * w.sK * 8, (void**)&w.Kb));
+  DFH_TRY(scratch_get(ctx, SCR_LMLCTL, WgGroupLayout::control_bytes(G), (void**)&w.ctl));
+  w.skip.assign((size_t)G, 0);
   std::vector<int> redo;                       // candidates for the lock-step schedule
-  for (int c0 = 0; c0 < nb; c0 += G) {
-    const int g = std::min(G, nb - c0);
-    GroupShape gs;
-    DFH_TRY(stage_group(a.descs, c0, g, kds, gs));
-    // pinned: descriptors | {aug. diagonal, mean, noise} [3 g] | (64-byte aligned) what comes back [3 g + 1]
-    const size_t up_par = (gs.blob_bytes + 15) & ~size_t(15), up_bytes = up_par + (size_t)g * 24;
-    const size_t back_off = (up_bytes + 63) & ~size_t(63), back_bytes = (size_t)(3 * g + 1) * 8;
-    void* pinned = nullptr;
-    DFH_TRY(pinned_get(ctx, back_off + back_bytes, &pinned));
-    char* hup = static_cast<char*>(pinned);
-    double* hpar = reinterpret_cast<double*>(hup + up_par);
-    const double* hred = reinterpret_cast<const double*>(hup + back_off);
-    const long long* hinfo = reinterpret_cast<const long long*>(hup + back_off) + 2 * g;
-    const unsigned long long* hstatus_p = reinterpret_cast<const unsigned long long*>(hup + back_off) + 3 * g;
-    void* blob = nullptr;
-    DFH_TRY(scratch_get(ctx, SCR_AUG2, up_bytes, &blob));
-    DFH_TRY(kerndev_stage_many(kds.data(), g, hup, blob, gs.blob_bytes));
-    double* dpar = reinterpret_cast<double*>(static_cast<char*>(blob) + up_par);
-    double* red = ctl;
-    long long* dinfo = reinterpret_cast<long long*>(ctl + 2 * g);
-    unsigned long long* d_status = reinterpret_cast<unsigned long long*>(ctl + 3 * g);
-    int* d_sync = reinterpret_cast<int*>(ctl + 3 * g + 1);
-    double *Xpb = nullptr, *Npb = nullptr;
-    DFH_TRY(scratch_get(ctx, SCR_XS, (size_t)g * n * gs.Pmax * 8, (void**)&Xpb));
-    DFH_TRY(scratch_get(ctx, SCR_XS2, (size_t)g * n * gs.parts_max * 8, (void**)&Npb));
-    for (int c = 0; c < g; ++c) {
-      // the augmented row's diagonal entry: c = 1 + |y - m|^2 / s2 > z.z (the eigenvalues of K + s2 I are >= s2)
-      // (|y - m|^2 = sum y^2 - 2 m sum y + n m^2: a bound needs no more than that, with a hair of slack for its rounding)
-      const double m = a.mean_consts ? a.mean_consts[c0 + c] : 0.0, s2 = a.noise_vars[c0 + c];
-      const double r2 = std::max(0.0, (sum_y2 - 2.0 * m * sum_y + (double)n * m * m)) * (1.0 + 1e-6) + 1e-6 * sum_y2;
-      hpar[c] = 1.0 + r2 / s2;
-      hpar[g + c] = m;
-      hpar[2 * g + c] = s2;
-      // (no noise, or a ratio beyond the double range: nothing bounds z.z -- such a candidate takes the lock-step schedule)
-      skip[c] = !(s2 > 0.0) || !std::isfinite(hpar[c]);
-      if (skip[c]) hpar[c] = 1.0;
-    }
-    DFH_HIP(hipMemcpyAsync(blob, hup, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-    // a group that leaves most of the device idle gets a TEAM of workgroups per candidate (lml_wg.h: lml_team_kernel)
-    int team = 1;
-    // (a timed-out hand-off costs ~0.1 s of polling plus the rebuilt group, and a slice sampler calls a hundred thousand
-    //  times: after one, the context's next 32 groups take one workgroup per candidate -- a shared device does not pay
-    //  the stall on every call; advisor, round 5)
-    const bool team_cooling = ctx->lml_team_cooldown > 0;
-    if (team_cooling) --ctx->lml_team_cooldown;
-    if (team_env != 0 && !team_cooling) {
-      const int cap = team_env > 0 ? team_env : 8;
-      while (team * 2 <= cap && (int64_t)team * 2 * g <= ctx->n_cu && team * 2 <= nbt) team *= 2;
-    }
-    auto run_group = [&](int tm) -> int {
-      {
-        SectionTimer t(ctx, DFH_T_KERNMAT);
-        DFH_TRY(build_group_grams(ctx, kds, g, gs, a.dX, n, a.d, Xpb, Npb, dpar + 2 * g, a.noise_vars + c0, Kb, sK, NP));
-      }
-      {
-        SectionTimer t(ctx, DFH_T_CHOL);
-        // failed pivots, status and the team's flags: one memset (the results in front of them are always written)
-        DFH_HIP(hipMemsetAsync(dinfo, 0, (size_t)(g + 1) * 8 + (tm > 1 ? (size_t)g * LMLT_SYNC_INTS * sizeof(int) : 0),
-                               ctx->stream));
-        DFH_TRY(lml_wg_batch(ctx, Kb, sK, NP, n, g, dy, dpar, red, dinfo, tm, d_status, d_sync));
-      }
-      DFH_HIP(hipMemcpyAsync(hup + back_off, ctl, back_bytes, hipMemcpyDeviceToHost, ctx->stream));
-      DFH_HIP(hipStreamSynchronize(ctx->stream));
-      return DFH_OK;
-    };
-    DFH_TRY(run_group(team));
-    if (team > 1 && *hstatus_p != 0) {
+  for (int c0 = 0; c0 < a.nb; c0 += G) {
+    DFH_TRY(wg_stage_group(a, w, c0, std::min(G, a.nb - c0)));
+    const int team = wg_pick_team(ctx, w.g, w.nbt);
+    DFH_TRY(wg_run_group(a, w, team));
+    if (team > 1 && w.lay.hstatus(w.pinned) != 0) {
       // a hand-off between the members of a team timed out (the device is shared, or not all of them were
       // resident): the matrices are rebuilt and every candidate gets ONE workgroup, which waits for nobody
       ++ctx->chol_fallbacks;
       ctx->lml_team_cooldown = 32;
-      DFH_TRY(run_group(1));
+      DFH_TRY(wg_run_group(a, w, 1));
     }
-    for (int c = 0; c < g; ++c) {
-      if (skip[c] || hinfo[c] != 0 || !std::isfinite(hred[2 * c]) || !std::isfinite(hred[2 * c + 1])) { redo.push_back(c0 + c); continue; }
-      if (a.jitter_powers) a.jitter_powers[c0 + c] = INT32_MIN;
-      a.lml_out[c0 + c] = lml_value(hred[2 * c], hred[2 * c + 1], n);
-    }
+    wg_collect(a, w, redo);
   }
   for (int c : redo) DFH_TRY(redo_alone(a, c));
+  return DFH_OK;
+}
+
+// ---- the routes that need no schedule ----
+
+// a projection is per matrix (96 GEMM steps each, psdproj.hip): every candidate is a fit of its own, as the candidates
+// that need the ladder are
+int lml_each_psd(const LmlCall& a) {
+  dfh_ctx* ctx = a.ctx;
+  const int64_t n = a.n, d = a.d;
+  std::vector<double> y_hold, yc((size_t)n);
+  const double* y_host = nullptr;
+  DFH_TRY(labels_on_host(ctx, a.y, n, a.flags, y_hold, &y_host));
+  double* dXown = nullptr;       // (the fit stages y through the workspaces; X must not sit in one of them)
+  DFH_TRY(dev_alloc(ctx, (size_t)n * d * 8, (void**)&dXown));
+  int rc = DFH_OK;
+  if (hipMemcpyAsync(dXown, a.dX, (size_t)n * d * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) rc = DFH_ERR_HIP;
+  for (int c = 0; c < a.nb && rc == DFH_OK; ++c) {
+    const double mc = a.mean_consts ? a.mean_consts[c] : 0.0;
+    for (int64_t i = 0; i < n; ++i) yc[(size_t)i] = y_host[i] - mc;
+    dfh_gp* g = nullptr;
+    rc = dfh_gp_fit(ctx, &a.descs[c], dXown, n, d, yc.data(), a.noise_vars[c], a.flags & (DFH_FIT_PSD_FLAGS | DFH_FIT_NO_JITTER), &g,
+                    a.lml_out + c, a.jitter_powers ? a.jitter_powers + c : nullptr);
+    if (g) dfh_gp_free(g);
+  }
+  dev_release(ctx, dXown);
+  return rc;
+}
+
+// Fused or Tiny: every candidate in one launch; a fused candidate whose pivot failed (the ladder), or whose augmented
+// pivot nothing bounds, is handed to the lock-step schedule on its own (the tiny kernels run the ladder themselves)
+int lml_one_launch(const LmlCall& a, LmlRoute route) {
+  dfh_ctx* ctx = a.ctx;
+  std::vector<double> ld_dot((size_t)a.nb * 2), y_hold;
+  std::vector<long long> info((size_t)a.nb, 0);
+  const double* y_host = nullptr;
+  DFH_TRY(labels_on_host(ctx, a.y, a.n, a.flags, y_hold, &y_host));
+  {
+    SectionTimer t(ctx, DFH_T_CHOL);
+    if (route == LmlRoute::Fused)
+      DFH_TRY(lml_wg_fused_batch(ctx, a.kds, a.nb, a.dX, a.n, a.d, y_host, a.noise_vars, a.mean_consts, ld_dot.data(), info.data()));
+    else
+      DFH_TRY(lml_tiny_batch(ctx, a.kds, a.nb, a.dX, a.n, a.d, y_host, a.noise_vars, a.mean_consts, !(a.flags & DFH_FIT_NO_JITTER),
+                             ld_dot.data(), a.jitter_powers));
+  }
+  for (int c = 0; c < a.nb; ++c) {
+    if (info[c] != 0) { DFH_TRY(redo_alone(a, c)); continue; }
+    if (route == LmlRoute::Fused && a.jitter_powers) a.jitter_powers[c] = INT32_MIN;
+    a.lml_out[c] = lml_value(ld_dot[2 * c], ld_dot[2 * c + 1], a.n);
+  }
   return DFH_OK;
 }
 
@@ -543,71 +672,16 @@ extern "C" int dfh_gp_lml_batch(dfh_ctx* ctx, const dfh_kernel_desc* descs, int3
   const double* dX = nullptr;
   if (flags & DFH_LML_X_IS_DEVICE) dX = X;
   else DFH_TRY(to_device(ctx, X, (size_t)n * d * 8, SCR_STAGE_A, &dX));
-  std::vector<double> y_hold;                  // the labels, when a route wants them on the host and they are not
-  const double* y_host = nullptr;
-  if (flags & DFH_FIT_PSD_FLAGS) {
-    // a projection is per matrix (96 GEMM steps each, psdproj.hip): every candidate is a fit of its own, as the
-    // candidates that need the ladder are
-    DFH_TRY(labels_on_host(ctx, y, n, flags, y_hold, &y_host));
-    std::vector<double> yc((size_t)n);
-    double* dXown = nullptr;       // (the fit stages y through the workspaces; X must not sit in one of them)
-    DFH_TRY(dev_alloc(ctx, (size_t)n * d * 8, (void**)&dXown));
-    int rc = DFH_OK;
-    if (hipMemcpyAsync(dXown, dX, (size_t)n * d * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) rc = DFH_ERR_HIP;
-    for (int c = 0; c < nb && rc == DFH_OK; ++c) {
-      const double mc = mean_consts ? mean_consts[c] : 0.0;
-      for (int64_t i = 0; i < n; ++i) yc[(size_t)i] = y_host[i] - mc;
-      dfh_gp* g = nullptr;
-      rc = dfh_gp_fit(ctx, &descs[c], dXown, n, d, yc.data(), noise_vars[c], flags & (DFH_FIT_PSD_FLAGS | DFH_FIT_NO_JITTER), &g,
-                      lml_out + c, jitter_powers ? jitter_powers + c : nullptr);
-      if (g) dfh_gp_free(g);
-    }
-    dev_release(ctx, dXown);
-    return rc;
+  std::vector<KernDev> kds((size_t)nb);        // host descriptors, built once: every route and a candidate's second try take slices
+  for (int c = 0; c < nb; ++c) DFH_TRY(kerndev_build_host(&descs[c], &kds[c]));
+  const LmlCall call = {ctx, descs, kds.data(), nb, dX, n, d, y, mean_consts, noise_vars, flags, lml_out, jitter_powers, 0};
+  const LmlRoute route = lml_route(call);
+  switch (route) {
+    case LmlRoute::PsdEach: return lml_each_psd(call);
+    case LmlRoute::Fused:
+    case LmlRoute::Tiny: return lml_one_launch(call, route);
+    case LmlRoute::Wg: return lml_batch_wg(call);
+    case LmlRoute::Lockstep: break;
   }
-  const LmlCall call = {ctx, descs, nb, dX, n, d, y, mean_consts, noise_vars, flags, lml_out, jitter_powers, 0};
-  static const bool tiny_enabled = env_flag("DFH_LML_TINY", true);
-  const bool fused_range = tiny_enabled && n > TINY64_MAX_N && n <= 255 && nb <= 64;
-  const bool tiny_range = tiny_enabled && n <= TINY_MAX_N;
-  if (fused_range || tiny_range) {
-    // host descriptors of every candidate, for the one-launch forms (gone again before the other schedules stage theirs)
-    std::vector<KernDev> all((size_t)nb);
-    for (int c = 0; c < nb; ++c) DFH_TRY(kerndev_build_host(&descs[c], &all[c]));
-    if (fused_range && lml_wg_fused_applies(all.data(), nb, n)) {
-      // a handful of mid-sized candidates (a slice sampler's call at 64 <= n <= 128): Gram matrix, factorisation and
-      // forward solve of each in ONE launch by one workgroup, nothing copied (lml_wg.h: lml_wgf_kernel)
-      std::vector<double> ld_dot((size_t)nb * 2);
-      std::vector<long long> info((size_t)nb);
-      DFH_TRY(labels_on_host(ctx, y, n, flags, y_hold, &y_host));
-      {
-        SectionTimer t(ctx, DFH_T_CHOL);
-        DFH_TRY(lml_wg_fused_batch(ctx, all.data(), nb, dX, n, d, y_host, noise_vars, mean_consts, ld_dot.data(), info.data()));
-      }
-      for (int c = 0; c < nb; ++c) {
-        if (info[c] != 0) {        // a failed pivot (the ladder) or no bound on the augmented pivot
-          DFH_TRY(redo_alone(call, c));
-          continue;
-        }
-        if (jitter_powers) jitter_powers[c] = INT32_MIN;
-        lml_out[c] = lml_value(ld_dot[2 * c], ld_dot[2 * c + 1], n);
-      }
-      return DFH_OK;
-    }
-    if (tiny_range && lml_tiny_applies(all.data(), nb, n)) {
-      // small problems: pack, Gram matrix, stable_cholesky and the solve of every candidate in ONE
-      // launch (lml_tiny.hip: k_lml_tiny)
-      std::vector<double> ld_dot((size_t)nb * 2);
-      DFH_TRY(labels_on_host(ctx, y, n, flags, y_hold, &y_host));
-      SectionTimer t(ctx, DFH_T_CHOL);
-      DFH_TRY(lml_tiny_batch(ctx, all.data(), nb, dX, n, d, y_host, noise_vars, mean_consts,
-                             !(flags & DFH_FIT_NO_JITTER), ld_dot.data(), jitter_powers));
-      for (int c = 0; c < nb; ++c) lml_out[c] = lml_value(ld_dot[2 * c], ld_dot[2 * c + 1], n);
-      return DFH_OK;
-    }
-  }
-  // one workgroup per candidate up to n = 2047 (DFH_LML_WG=0: the lock-step schedule for every n)
-  static const int wg_min_batch = env_int("DFH_LML_WG_MIN_BATCH", 1);
-  static const bool wg_enabled = env_flag("DFH_LML_WG", true);
-  if (wg_enabled && n <= LMLWG_MAX_N && nb >= wg_min_batch) return lml_batch_wg(call);
   return lml_batch_lockstep(call);
 }

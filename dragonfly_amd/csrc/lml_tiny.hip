@@ -1,7 +1,7 @@
 // The whole tuning objective of a SMALL problem in one launch (k_lml_tiny, n <= TINY_MAX_N; k_lml_tiny64, n <= 63, on
 // the 64 x 64 machinery of factor64.h), the pinned staging blob both share with the fused one-workgroup form of
-// lml_wg.h (tiny_blob_build, tiny_poll_results) and the host launcher.  The dispatcher is lml.hip.
-#include "common.h"
+// lml_wg.h (tiny_blob_build, tiny_arm_results, tiny_poll_results) and the host launcher.  The route chooser is lml.hip.
+#include "lml.h"
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -369,17 +369,6 @@ __global__ __launch_bounds__(256, 1) void k_lml_tiny64(TinyArgs a) {
 }  // namespace
 
 
-bool lml_tiny_applies(const KernDev* kds, int count, int64_t n) {
-  if (n > TINY_MAX_N) return false;
-  for (int c = 0; c < count; ++c)
-    if (kds[c].P > TINY_MAX_P || kds[c].n_parts > TINY_MAX_PARTS || kds[c].P < 1 || !kds[c].stationary || kds[c].esp)
-      return false;
-  return true;
-}
-
-// logdet_dot[2c], [2c+1] = sum(log(diag(L_c))), (y - m_c)^T (K_c + noise_c I)^-1 (y - m_c);
-// powers[c] = jitter power used (INT32_MIN: none).  Returns DFH_ERR_NOT_PD / DFH_ERR_JITTER as the
-// one-fit path would.
 int tiny_blob_build(dfh_ctx* ctx, const KernDev* kds, int count, int64_t n, const double* y_host,
                     const double* noise_vars, const double* mean_consts, TinyBlob* tb) {
   std::vector<size_t> image_off((size_t)count);
@@ -426,8 +415,13 @@ int tiny_blob_build(dfh_ctx* ctx, const KernDev* kds, int count, int64_t n, cons
   return DFH_OK;
 }
 
-// Host side of a direct call's results: the kernel's status words (res[4 c + 3], -1.0 before the launch) polled in the
-// pinned buffer; past the budget the stream is synchronised like any other call and a kernel that never wrote is an error.
+// Host side of a direct call's results: the kernel's status words (res[4 c + 3]; the kernel's status is 0, 1 or 2) set
+// to -1.0, "not there yet", before the launch and polled in the pinned buffer after it; past the budget the stream is
+// synchronised like any other call and a kernel that never wrote is an error.
+void tiny_arm_results(volatile double* vres, int count) {
+  for (int c = 0; c < count; ++c) vres[4 * c + 3] = -1.0;
+}
+
 int tiny_poll_results(dfh_ctx* ctx, volatile double* vres, int count, const char* what) {
   bool all_in = false;
   const auto t_start = std::chrono::steady_clock::now();
@@ -447,6 +441,7 @@ int tiny_poll_results(dfh_ctx* ctx, volatile double* vres, int count, const char
   return DFH_OK;
 }
 
+// Returns DFH_ERR_NOT_PD / DFH_ERR_JITTER as the one-fit path would.
 int lml_tiny_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double* dX, int64_t n, int64_t ldx,
                    const double* y_host, const double* noise_vars, const double* mean_consts,
                    bool allow_jitter, double* logdet_dot, int32_t* powers) {
@@ -485,8 +480,7 @@ int lml_tiny_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double* dX
   a.stamps = (want_stamps && count <= 64) ? d_stamps : nullptr;
 #endif
   volatile double* vres = res;
-  if (direct)
-    for (int c = 0; c < count; ++c) vres[4 * c + 3] = -1.0;      // "not there yet": the kernel's status is 0, 1 or 2
+  if (direct) tiny_arm_results(vres, count);
   static bool attr_set[DFH_MAX_DEVICES] = {false};
   if (!attr_set[ctx->device]) {
     DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_lml_tiny), hipFuncAttributeMaxDynamicSharedMemorySize,

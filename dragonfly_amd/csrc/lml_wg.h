@@ -1,7 +1,7 @@
 // The tuning objective of one hyper-parameter candidate in one launch by ONE workgroup (lml_wg_kernel; lml_wgf_kernel
 // with the Gram matrix built in the same launch) or by a TEAM of workgroups (lml_team_kernel), and their host launchers.
-// The dispatcher that chooses between them, the small-problem kernels of lml_tiny.hip and the lock-step schedule is
-// lml.hip.  The kernels factor with factor64_waves and run the row solve of diag_step64_kernel on the same LDS images.
+// The route chooser that picks between them, the small-problem kernels of lml_tiny.hip and the lock-step schedule is
+// lml.hip; lml.h declares what the three share.  The kernels factor with factor64_waves and run the row solve of diag_step64_kernel on the same LDS images.
 //
 // NOT a translation unit of its own: chol.hip includes this file at file scope, behind diag_step64_kernel and after
 // factor64.h.  These kernels call out-of-line device functions (lmlwg_factor_last, lmlt_factor_tile), so their register
@@ -10,6 +10,7 @@
 // allocation; inside chol.hip's unit every function is instruction for instruction what it was when this code stood
 // in chol.hip itself (profiles/chol_split_kernel_resource_usage.txt).
 #pragma once
+#include "lml.h"
 
 namespace {
 
@@ -716,19 +717,13 @@ __global__ __launch_bounds__(256, 1) void lml_team_kernel(LmlWgArgs a) {
 
 }  // namespace
 
-// Launch of lml_wg_kernel: `count` candidates, one workgroup each (K: padded matrices of order 64 * ceil((n + 1) / 64),
-// see the kernel).  d_par: [count] augmented diagonal entries, then [count] prior means; d_out2: [count][2];
-// d_info: [count] failing pivots (zeroed here).  Asynchronous on ctx->stream.
-// team > 1: `team` workgroups per candidate (lml_team_kernel; team * count should not exceed the CUs).  d_status
-// (device, 8 bytes, or null when team == 1) is zeroed here and non-zero afterwards iff a hand-off wait expired:
-// the results of the launch are then void.
+// Launch of lml_wg_kernel (team == 1) or lml_team_kernel (lml.h: lml_wg_batch), asynchronous on ctx->stream.
+// d_par: [count] augmented diagonal entries, then [count] prior means.  The caller has zeroed d_info, d_status and the
+// team's flags d_sync in one block (one memset per group).
 int lml_wg_batch(dfh_ctx* ctx, double* K, int64_t sK, int64_t ld, int64_t n, int count, const double* d_y,
-                 const double* d_par, double* d_out2, long long* d_info, int team, unsigned long long* d_status,
-                 int* d_sync_zeroed) {
-  // d_sync_zeroed: the team's flags ([count][LMLT_SYNC_INTS]) in a block the caller has ALREADY zeroed together with
-  // d_info and d_status (one memset per group instead of three); null: allocated and zeroed here.
+                 const double* d_par, double* d_out2, long long* d_info, int team, unsigned long long* d_status, int* d_sync) {
   DFH_ARG(ctx && K && d_y && d_par && d_out2 && d_info && n >= 1 && n <= LMLWG_MAX_N && count >= 1 && team >= 1 &&
-          team <= 32 && (team == 1 || d_status));
+          team <= 32 && (team == 1 || (d_status && d_sync)));
   const int64_t nbt = (n + 1 + PB - 1) / PB;
   DFH_ARG(ld >= nbt * PB && (ld & 1) == 0 && sK >= nbt * PB * ld && (reinterpret_cast<uintptr_t>(K) & 15) == 0);
   static bool attr_set_dev[DFH_MAX_DEVICES] = {false};
@@ -740,7 +735,6 @@ int lml_wg_batch(dfh_ctx* ctx, double* K, int64_t sK, int64_t ld, int64_t n, int
                                 LMLT_SMEM));
     attr_set = true;
   }
-  if (!d_sync_zeroed) DFH_HIP(hipMemsetAsync(d_info, 0, (size_t)count * 8, ctx->stream));
   LmlWgArgs a;
   a.K = K; a.sK = (long)sK; a.ld = (long)ld; a.n = (int)n; a.nbt = (int)nbt;
   a.y = d_y; a.par = d_par; a.count = count; a.out2 = d_out2; a.info = d_info;
@@ -751,13 +745,7 @@ int lml_wg_batch(dfh_ctx* ctx, double* K, int64_t sK, int64_t ld, int64_t n, int
     return DFH_OK;
   }
   DFH_TRY(scratch_get(ctx, SCR_CHOLINV, (size_t)count * nbt * LMLT_LINV * 8, (void**)&a.linvbuf));
-  if (d_sync_zeroed) {
-    a.sync = d_sync_zeroed;
-  } else {
-    DFH_TRY(scratch_get(ctx, SCR_CHOLSYNC, (size_t)count * LMLT_SYNC_INTS * sizeof(int), (void**)&a.sync));
-    DFH_HIP(hipMemsetAsync(a.sync, 0, (size_t)count * LMLT_SYNC_INTS * sizeof(int), ctx->stream));
-    DFH_HIP(hipMemsetAsync(d_status, 0, 8, ctx->stream));
-  }
+  a.sync = d_sync;
   static const int spin_limit = env_int("DFH_TEST_SPIN_LIMIT", LMLT_SPIN_LIMIT_DEFAULT);     // (factor64.h: why not the factorisation's)
   a.spin_limit = spin_limit;
 #ifdef DFH_DEBUG_HOOKS
@@ -768,20 +756,22 @@ int lml_wg_batch(dfh_ctx* ctx, double* K, int64_t sK, int64_t ld, int64_t n, int
   return DFH_OK;
 }
 
-bool lml_wg_fused_applies(const KernDev* kds, int count, int64_t n) {
-  static const int fused_max = env_int("DFH_LML_FUSED", 16);       // candidates per call; 0: off
-  static const int max_n = std::min(255, env_int("DFH_LML_FUSED_MAX_N", (int)LMLF_MAX_N));
-  if (count < 1 || count > fused_max || n < 1 || n > max_n) return false;
+LmlFusedLimits lml_fused_limits() {
+  static const LmlFusedLimits lim = {env_int("DFH_LML_FUSED", 16), env_int("DFH_LML_FUSED_MAX_N", (int)LMLF_MAX_N)};
+  return lim;
+}
+
+bool lml_fused_fits_lds(const KernDev* kds, int count, int64_t n) {
   for (int c = 0; c < count; ++c)
-    if (kds[c].P > TINY_MAX_P || kds[c].n_parts > TINY_MAX_PARTS || kds[c].P < 1 || !kds[c].stationary || kds[c].esp ||
-        n * (int64_t)(kds[c].P + kds[c].n_parts) > LMLF_LDS_DOUBLES) return false;
+    if (n * (int64_t)(kds[c].P + kds[c].n_parts) > LMLF_LDS_DOUBLES) return false;
   return true;
 }
 
 int lml_wg_fused_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double* dX, int64_t n, int64_t ldx,
                        const double* y_host, const double* noise_vars, const double* mean_consts,
                        double* logdet_dot, long long* info) {
-  DFH_ARG(ctx && kds && dX && y_host && noise_vars && logdet_dot && info && lml_wg_fused_applies(kds, count, n));
+  DFH_ARG(ctx && kds && dX && y_host && noise_vars && logdet_dot && info && count >= 1 && n >= 1 && n <= LMLF_KERNEL_MAX_N &&
+          lml_one_launch_kernels(kds, count) && lml_fused_fits_lds(kds, count, n));
   const int64_t nbt = (n + 1 + PB - 1) / PB, NP = PB * nbt, sK = NP * NP;
   static bool attr_set_dev[DFH_MAX_DEVICES] = {false};
   if (!attr_set_dev[ctx->device]) {
@@ -804,7 +794,7 @@ int lml_wg_fused_batch(dfh_ctx* ctx, const KernDev* kds, int count, const double
   f.blob = tb.host; f.y_off = (long)tb.y_off;
   f.ybuf = ybuf; f.out4 = tb.res; f.direct = 1;
   volatile double* vres = tb.res;
-  for (int c = 0; c < count; ++c) vres[4 * c + 3] = -1.0;          // "not there yet"
+  tiny_arm_results(vres, count);
   hipLaunchKernelGGL(lml_wgf_kernel, dim3((unsigned)count), dim3(256), DIAG_STEP_SMEM, ctx->stream, a, f);
   DFH_LAUNCH_CHECK();
   DFH_TRY(tiny_poll_results(ctx, vres, count, "lml_wgf_kernel"));
