@@ -108,6 +108,11 @@ SIGNATURES = {
                             C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
   'dfh_gp_add_ucb_group': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
                                      C.c_void_p, c_double_p, c_int64_p]),
+  'dfh_mf_add_ucb_group': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                     C.c_void_p, c_double_p, c_int64_p]),
+  'dfh_mf_add_ucb_all': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+  'dfh_join_fixed_columns': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
   'dfh_mo_ucb_argmax': (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_int64_p]),
   'dfh_mo_ts_argmax': (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -332,9 +332,12 @@ int kernmat_gram(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bool
                  double* K, int64_t ldk, bool lower_only = false);
 // kernmat_cross: K(pts1, pts2).  mean: out[pts1.n] = K alpha is wanted from the same pass; done tells whether the kernel
 // that ran could do it -- the caller multiplies itself otherwise.
+// col_w (device, [pts2.n]; one SE / Matern part only): K[a][i] = col_w[i] * k_part(pts1_a, pts2_i) -- the part on its
+// own, without the kernel's outer scale or its other factors (apply_outer is not read); the weight is in before the store,
+// so whatever is formed from K afterwards (the mean, the solve) is weighted.  No kernel with col_w fuses the mean.
 struct KmMean { const double* alpha; double* out; bool done; };
 int kernmat_cross(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bool apply_outer, KmPts pts1, KmPts pts2,
-                  double* K, int64_t ldk, KmMean* mean = nullptr);
+                  double* K, int64_t ldk, KmMean* mean = nullptr, const double* col_w = nullptr);
 
 // Blocked Cholesky, in place on the lower triangle of the row-major matrix A (upper part of the
 // off-diagonal blocks is left untouched; the upper part of the 64x64 diagonal blocks is zeroed).

@@ -54,6 +54,7 @@ struct ChunkReq {
   bool want_var = true;                 // solve the cross matrix into V^T (and fill ss / ss2)
   const Halluc* h = nullptr;            // block form of the points in progress: the second block row as well
   int parity = 0;                       // which set of chunk buffers (the pipelined Thompson sampling alternates)
+  const double* col_w = nullptr;        // one weight per training row on the cross matrix (kernmat_cross: col_w; gp_mf.hip)
 };
 struct ChunkOut {                       // where posterior_chunk left things (scratch of the request's parity)
   double* Xsp = nullptr; double* Nsp = nullptr;   // the packed candidates
@@ -76,6 +77,7 @@ struct EvalReq {
   int64_t m = 0, ldxs = 0;
   int part_lo = 0, part_hi = -1;                  // as ChunkReq
   bool pre_gathered = false;
+  const double* col_w = nullptr;                  // as ChunkReq (device, [n])
   double kxx = 0.0;                               // prior variance of a stationary part range
   const double* Xh = nullptr; int64_t q = 0;      // points in progress
   double mean_const = 0.0;
@@ -117,6 +119,16 @@ struct ChunkStager {
   }
 };
 
+// What the stacked add-UCB calls differ in (add_ucb_stacked): the additive kernel's groups, or the groups of a
+// multi-fidelity GP's additive domain factor at a fixed fidelity (gp_mf.hip)
+struct StackedGroups {
+  int part0 = 0, G = 0;                 // the groups are the kernel's parts [part0, part0 + G)
+  const double* col_w = nullptr;        // weights of the training rows (ChunkReq::col_w), or null
+  double prior_scale = 1.0;             // prior variance of group g = prior_scale * k_g(x, x)
+  // the per-group route, taken when the stack does not fit one posterior chunk
+  std::function<int(int g, double beta, const double* Xg, int64_t m, double* vals, double* best_val, int64_t* best_idx)> one_group;
+};
+
 struct DevBlock {           // dev_alloc'ed memory of one call
   dfh_ctx* ctx; void* p = nullptr;
   explicit DevBlock(dfh_ctx* c) : ctx(c) {}
@@ -131,6 +143,9 @@ struct DevBlock {           // dev_alloc'ed memory of one call
 bool free_plus_own_scratch(dfh_ctx* ctx, size_t* bytes);     // free device memory + the context's own scratch; false: unknown
 int64_t pick_chunk(dfh_ctx* ctx, int64_t n, int64_t m);      // candidate rows per posterior chunk
 int halluc_resolve(dfh_gp* gp, const double* Xh, int64_t q, HallucScope* s);
+int add_ucb_stacked(dfh_gp* gp, const StackedGroups& sg, const double* betas, const double* Xg_all, const int64_t* m_per_group,
+                    double* vals_out, double* best_vals, int64_t* best_idx);
+int gp_eval_driver(dfh_gp* gp, const EvalReq& rq);          // predict / acquisition arg-max / add-UCB of one group, chunk by chunk
 // One chunk of candidates (device pointer Xs_dev, mc rows): fills mu_raw, ss (and ss2 with rq.h)
 int posterior_chunk(dfh_gp* gp, const double* Xs_dev, int64_t mc, int64_t ldxs, const ChunkReq& rq, double* mu_raw,
                     double* ss, double* ss2, ChunkOut* out = nullptr);

@@ -372,7 +372,7 @@ int posterior_chunk(dfh_gp* gp, const double* Xs_dev, int64_t mc, int64_t ldxs, 
     DFH_TRY(pack_scaled(ctx, kd, rq.part_lo, part_hi, rq.pre_gathered, Xs_dev, mc, ldxs, o.Xsp, o.Nsp));
     KmMean mean{gp->alpha, mu_raw, false};      // gp_core.py:174, from the same pass where the kernel can
     DFH_TRY(kernmat_cross(ctx, kd, rq.part_lo, part_hi, true, KmPts{o.Xsp, o.Nsp, mc}, KmPts{gp->Xp, gp->Np, gp->n}, o.Kct, gp->n,
-                          &mean));
+                          &mean, rq.col_w));
     if (!mean.done) DFH_TRY(gemv_rows(ctx, o.Kct, mc, gp->n, gp->n, gp->alpha, 1.0, nullptr, 0.0, mu_raw));
   }
   if (rq.want_var) {
@@ -390,7 +390,7 @@ int posterior_chunk(dfh_gp* gp, const double* Xs_dev, int64_t mc, int64_t ldxs, 
 }
 
 // shared driver for predict / acquisition arg-max
-static int gp_eval_driver(dfh_gp* gp, const EvalReq& rq) {
+int gp_eval_driver(dfh_gp* gp, const EvalReq& rq) {
   dfh_ctx* ctx = gp->ctx;
   DFH_HIP(hipSetDevice(ctx->device));
   const int64_t m = rq.m;
@@ -416,6 +416,7 @@ static int gp_eval_driver(dfh_gp* gp, const EvalReq& rq) {
   const double p0 = rq.params ? rq.params[0] : 0.0, p1 = rq.params ? rq.params[1] : 0.0;
   ChunkReq creq;
   creq.part_lo = rq.part_lo; creq.part_hi = rq.part_hi; creq.pre_gathered = rq.pre_gathered;
+  creq.col_w = rq.col_w;
   for (int64_t i0 = 0; i0 < m; i0 += mc_max) {
     const int64_t mc = std::min(mc_max, m - i0);
     const double* xs_c = nullptr;
@@ -506,34 +507,31 @@ extern "C" int dfh_gp_add_ucb_group(dfh_gp* gp, int32_t group, double beta, cons
   return gp_eval_driver(gp, rq);
 }
 
-// All additive groups at once: the per-group cross matrices are stacked into one (sum m_g) x n
+// The groups of an additive model at once: the per-group cross matrices are stacked into one (sum m_g) x n
 // matrix so that the posterior solve is ONE triangular solve with sum(m_g) right-hand sides instead
 // of G small ones (the reference issues G solve_lower_triangular calls, gpb_acquisitions.py:161-176).
 // Xg_all: group g's candidates [m_g x |group g|], back to back.  Falls back to the per-group
 // route when the stack does not fit one posterior chunk.
-extern "C" int dfh_gp_add_ucb_all(dfh_gp* gp, const double* betas, const double* Xg_all, const int64_t* m_per_group,
-                                  double* vals_out, double* best_vals, int64_t* best_idx) {
-  DFH_ARG(gp && betas && Xg_all && m_per_group && best_vals && best_idx);
-  DFH_ARG(!gp->gram);
-  DFH_ARG(gp->kd.multi && !gp->kd.product && !gp->kd.esp);     // additive kernels only
+int add_ucb_stacked(dfh_gp* gp, const StackedGroups& sg, const double* betas, const double* Xg_all, const int64_t* m_per_group,
+                    double* vals_out, double* best_vals, int64_t* best_idx) {
   dfh_ctx* ctx = gp->ctx;
   DFH_HIP(hipSetDevice(ctx->device));
   const KernDev& kd = gp->kd;
-  const int G = kd.n_parts;
+  const int G = sg.G, p0 = sg.part0;
   const int64_t n = gp->n;
   std::vector<int64_t> off(G + 1, 0), xoff(G + 1, 0);
   std::vector<int> gdim(G, 0);
   for (int g = 0; g < G; ++g) {
     DFH_ARG(m_per_group[g] >= 1);
-    for (int c = 0; c < kd.parts[g].kc; ++c) gdim[g] += kd.cols[kd.parts[g].poff + c] >= 0;
+    for (int c = 0; c < kd.parts[p0 + g].kc; ++c) gdim[g] += kd.cols[kd.parts[p0 + g].poff + c] >= 0;
     off[g + 1] = off[g] + m_per_group[g];
     xoff[g + 1] = xoff[g] + m_per_group[g] * gdim[g];
   }
   const int64_t M = off[G];
   if (M > pick_chunk(ctx, n, M)) {
     for (int g = 0; g < G; ++g)
-      DFH_TRY(dfh_gp_add_ucb_group(gp, g, betas[g], Xg_all + xoff[g], m_per_group[g],
-                                   vals_out ? vals_out + off[g] : nullptr, &best_vals[g], &best_idx[g]));
+      DFH_TRY(sg.one_group(g, betas[g], Xg_all + xoff[g], m_per_group[g], vals_out ? vals_out + off[g] : nullptr,
+                           &best_vals[g], &best_idx[g]));
     return DFH_OK;
   }
   const double* dXg = nullptr;
@@ -555,11 +553,11 @@ extern "C" int dfh_gp_add_ucb_all(dfh_gp* gp, const double* betas, const double*
     bool mu_all = true;          // posterior means from the cross-matrix pass itself where the kernel can
     for (int g = 0; g < G; ++g) {
       double* Xsp_g = Xsp + off[g] * kd.P; double* Nsp_g = Nsp + off[g] * kd.n_parts;
-      DFH_TRY(pack_scaled(ctx, kd, g, g + 1, true, dXg + xoff[g], m_per_group[g], gdim[g], Xsp_g, Nsp_g));
-      // K_j(X*_j, X[:, group j]) with the outer scale        (gpb_acquisitions.py:166-168)
+      DFH_TRY(pack_scaled(ctx, kd, p0 + g, p0 + g + 1, true, dXg + xoff[g], m_per_group[g], gdim[g], Xsp_g, Nsp_g));
+      // K_j(X*_j, X[:, group j]) with the outer scale        (gpb_acquisitions.py:166-168; weighted: :364-366)
       KmMean mean{gp->alpha, mu_raw + off[g], false};
-      DFH_TRY(kernmat_cross(ctx, kd, g, g + 1, true, KmPts{Xsp_g, Nsp_g, m_per_group[g]}, KmPts{gp->Xp, gp->Np, n},
-                            Kct + off[g] * n, n, &mean));
+      DFH_TRY(kernmat_cross(ctx, kd, p0 + g, p0 + g + 1, true, KmPts{Xsp_g, Nsp_g, m_per_group[g]}, KmPts{gp->Xp, gp->Np, n},
+                            Kct + off[g] * n, n, &mean, sg.col_w));
       mu_all = mu_all && mean.done;
     }
     if (!mu_all) DFH_TRY(gemv_rows(ctx, Kct, M, n, n, gp->alpha, 1.0, nullptr, 0.0, mu_raw));
@@ -571,12 +569,12 @@ extern "C" int dfh_gp_add_ucb_all(dfh_gp* gp, const double* betas, const double*
   SectionTimer t(ctx, DFH_T_ACQ);
   DFH_TRY(row_sumsq(ctx, Kct, M, n, n, ss));
   for (int g = 0; g < G; ++g) {
-    const double kxx = kd.outer_scale * kerndev_part_kxx(kd, g);        // kern_scale * kernel_j(x, x)
+    const double kxx = sg.prior_scale * kerndev_part_kxx(kd, p0 + g);   // kern_scale * kernel_j(x, x)
     const int64_t mg = m_per_group[g];
     const double* kss_g = nullptr;
-    if (!part_is_stationary(kd, g)) {
+    if (!part_is_stationary(kd, p0 + g)) {
       // a polynomial group: its prior variance depends on the point
-      DFH_TRY(prior_diag(ctx, kd, Xsp + off[g] * kd.P, Nsp + off[g] * kd.n_parts, mg, kss_w + off[g], g, g + 1));
+      DFH_TRY(prior_diag(ctx, kd, Xsp + off[g] * kd.P, Nsp + off[g] * kd.n_parts, mg, kss_w + off[g], p0 + g, p0 + g + 1));
       kss_g = kss_w + off[g];
     }
     hipLaunchKernelGGL(k_posterior_acq, dim3((unsigned)((mg + 255) / 256)), dim3(256), 0, ctx->stream, (int)DFH_ACQ_UCB,
@@ -598,6 +596,20 @@ extern "C" int dfh_gp_add_ucb_all(dfh_gp* gp, const double* betas, const double*
   if (vals_out) DFH_TRY(from_device(ctx, vals_out, val, (size_t)M * 8));
   DFH_HIP(hipStreamSynchronize(ctx->stream));
   return DFH_OK;
+}
+
+// Every group of the additive kernel: parts [0, n_parts), the kernel's outer scale, no weights
+extern "C" int dfh_gp_add_ucb_all(dfh_gp* gp, const double* betas, const double* Xg_all, const int64_t* m_per_group,
+                                  double* vals_out, double* best_vals, int64_t* best_idx) {
+  DFH_ARG(gp && betas && Xg_all && m_per_group && best_vals && best_idx);
+  DFH_ARG(!gp->gram);
+  DFH_ARG(gp->kd.multi && !gp->kd.product && !gp->kd.esp);     // additive kernels only
+  StackedGroups sg;
+  sg.part0 = 0; sg.G = gp->kd.n_parts; sg.prior_scale = gp->kd.outer_scale;
+  sg.one_group = [gp](int g, double beta, const double* Xg, int64_t m, double* vals, double* bv, int64_t* bi) {
+    return dfh_gp_add_ucb_group(gp, g, beta, Xg, m, vals, bv, bi);
+  };
+  return add_ucb_stacked(gp, sg, betas, Xg_all, m_per_group, vals_out, best_vals, best_idx);
 }
 
 extern "C" int dfh_gp_predict_covar(dfh_gp* gp, const double* Xs, int64_t m, const double* Xh, int64_t q,

@@ -18,6 +18,7 @@ struct KmCall {
   bool lower_only;             // (symmetric) the tiles on and below the diagonal only
   double* K; int64_t ldk;
   KmMean* mean;                // (cross) the product with a vector is wanted from the same pass, or null
+  const double* col_w = nullptr;   // (cross, one stationary part) K[a][i] = col_w[i] * k_part(a, i): the part alone, no outer scale
 };
 
 // DFH_KM_* / DFH_PACK_FUSED, read once per process
@@ -45,6 +46,7 @@ int km_launch_strip(dfh_ctx* ctx, const KmCall& c);         // sets c.mean->done
 // km_esp.hip, km_generic.hip: every call of an ESP kernel; whatever no other route takes
 int km_launch_esp(dfh_ctx* ctx, const KmCall& c);
 int km_launch_generic(dfh_ctx* ctx, const KmCall& c);
+int km_launch_colw(dfh_ctx* ctx, const KmCall& c);          // km_generic.hip: a call with col_w
 #pragma GCC visibility pop
 
 namespace {

@@ -29,6 +29,7 @@ static int kernmat_dispatch(dfh_ctx* ctx, const KmCall& c) {
   if (c.mean) c.mean->done = false;
   if (c.a.n <= 0 || c.b.n <= 0) return DFH_OK;
   DFH_ARG(c.a.n < (1LL << 31) && c.b.n < (1LL << 31));
+  if (c.col_w) return km_launch_colw(ctx, c);      // weighted columns: one route knows them
   if (c.kd->esp) {             // the whole ESP kernel in one kernel of its own; no fused posterior mean
     DFH_ARG(c.part_lo == 0 && c.part_hi == c.kd->n_parts && c.apply_outer);
     return km_launch_esp(ctx, c);
@@ -48,6 +49,6 @@ int kernmat_gram(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bool
 }
 
 int kernmat_cross(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bool apply_outer, KmPts pts1, KmPts pts2,
-                  double* K, int64_t ldk, KmMean* mean) {
-  return kernmat_dispatch(ctx, KmCall{&kd, part_lo, part_hi, apply_outer, pts1, pts2, false, 0.0, false, K, ldk, mean});
+                  double* K, int64_t ldk, KmMean* mean, const double* col_w) {
+  return kernmat_dispatch(ctx, KmCall{&kd, part_lo, part_hi, apply_outer, pts1, pts2, false, 0.0, false, K, ldk, mean, col_w});
 }

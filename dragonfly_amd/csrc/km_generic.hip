@@ -206,6 +206,98 @@ __global__ __launch_bounds__(256, 2) void kernmat_kernel(KmArgs p) {
   }
 }
 
+// One SE / Matern part on its own with a weight per column: K[a][i] = col_w[i] * k_part(a, i), no outer scale and no
+// other part -- the cross matrix of one group of a multi-fidelity GP's additive domain model at a fixed fidelity, where
+// col_w[i] = kern_scale * k_fid(z*, Z_i) (opt/gpb_acquisitions.py:364-366; gp_mf.hip).  The single-part path of
+// kernmat_kernel<4, false> -- its 128 x 128 tile, operand staging, distance expansion and kern_eval -- with one load and one
+// multiplication more per element, right before the store, so that no m x n scaling pass reads and writes the matrix
+// again ahead of the solve.  A kernel of its own: kernmat_kernel's instances stay the code objects they were.
+__global__ __launch_bounds__(256, 2) void kernmat_colw_kernel(KmArgs p, const double* __restrict__ col_w) {
+  constexpr int TJ = 4, BN = 2 * TJ * 16;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double* As = smem;                           // [128][KM_KP]
+  double* Bs = As + KM_BM * KM_KP;             // [BN][KM_KP]
+  double* na = Bs + BN * KM_KP;                // [128]
+  double* nb = na + KM_BM;                     // [BN]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const long m0 = (long)blockIdx.y * KM_BM, n0 = (long)blockIdx.x * BN;
+  const int part = p.part_lo;
+  const PartDev& pd = p.parts[part];            // stays in global memory: uniform scalar loads
+
+  double4_t acc[4][TJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
+
+  for (int k0 = 0; k0 < pd.kc; k0 += KM_KC) {
+    const int kc = min(KM_KC, pd.kc - k0);     // multiple of 4
+    const int kh = kc >> 1;                    // double2 per row
+    __syncthreads();                           // previous readers of As/Bs are done
+    for (int idx = tid; idx < KM_BM * kh; idx += 256) {
+      const int r = idx / kh, c2 = (idx - r * kh) * 2;
+      const long row = m0 + r;
+      double2_t v = (double2_t){0.0, 0.0};
+      if (row < p.n1) v = *reinterpret_cast<const double2_t*>(p.Xp1 + row * p.P + pd.poff + k0 + c2);
+      *reinterpret_cast<double2_t*>(As + r * KM_KP + c2) = v;
+    }
+    for (int idx = tid; idx < BN * kh; idx += 256) {
+      const int r = idx / kh, c2 = (idx - r * kh) * 2;
+      const long row = n0 + r;
+      double2_t v = (double2_t){0.0, 0.0};
+      if (row < p.n2) v = *reinterpret_cast<const double2_t*>(p.Xp2 + row * p.P + pd.poff + k0 + c2);
+      *reinterpret_cast<double2_t*>(Bs + r * KM_KP + c2) = v;
+    }
+    if (k0 == 0) {
+      if (tid < KM_BM) {
+        const long row = m0 + tid;
+        na[tid] = row < p.n1 ? p.Np1[row * p.n_parts_total + part] : 0.0;
+      } else {
+        const long row = n0 + tid - KM_BM;
+        nb[tid - KM_BM] = row < p.n2 ? p.Np2[row * p.n_parts_total + part] : 0.0;
+      }
+    }
+    __syncthreads();
+    const double* as = As + (wm * 64 + l15) * KM_KP + l4;
+    const double* bs = Bs + (wn * TJ * 16 + l15) * KM_KP + l4;
+    for (int kk = 0; kk < kc; kk += 4) {
+      double a[4], b[TJ];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) a[t] = as[t * 16 * KM_KP + kk];
+#pragma unroll
+      for (int t = 0; t < TJ; ++t) b[t] = bs[t * 16 * KM_KP + kk];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < TJ; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+  }
+
+  const ExpConsts& ec = p.ec;                  // kernel arguments: scalar loads, SGPR-resident
+#pragma unroll
+  for (int j = 0; j < TJ; ++j) {
+    const int lc = wn * TJ * 16 + j * 16 + l15;
+    const long col = n0 + lc;
+    if (col >= p.n2) continue;
+    const double w = col_w[col], nbj = nb[lc];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int lr = wm * 64 + i * 16 + l4 + 4 * r;
+        const long row = m0 + lr;
+        double dsq = (nbj + na[lr]) - 2.0 * acc[i][j][r];       // general_utils.py:66-68
+        dsq = dsq < 0.0 ? 0.0 : dsq;                             // np.clip(.,0,inf), NaN kept
+        if (row < p.n1) p.K[row * p.ldk + col] = w * kern_eval(pd, dsq, ec);
+      }
+    }
+  }
+}
+
 using KmKernel = void (*)(KmArgs);
 constexpr int SM4 = ((KM_BM + 128) * KM_KP + KM_BM + 128) * 8;
 constexpr int SM2 = ((KM_BM + 64) * KM_KP + KM_BM + 64) * 8;
@@ -235,6 +327,8 @@ int set_lds_limits(dfh_ctx* ctx) {
                              kernmat_kernel<2, true, true, true, true>};
   for (KmKernel fn : multi)
     DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, SM2));
+  DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernmat_colw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              SM4));
   attr_set = true;
   return DFH_OK;
 }
@@ -258,5 +352,17 @@ int km_launch_generic(dfh_ctx* ctx, const KmCall& c) {
     hipLaunchKernelGGL(fn, grid, dim3(256), smem, ctx->stream, b);
     DFH_LAUNCH_CHECK();
   }
+  return DFH_OK;
+}
+
+// A weighted cross matrix (KmCall::col_w): one stationary part of any kernel, alone
+int km_launch_colw(dfh_ctx* ctx, const KmCall& c) {
+  DFH_ARG(c.col_w && !c.symmetric && !c.kd->esp && c.part_hi == c.part_lo + 1 && part_is_stationary(*c.kd, c.part_lo));
+  DFH_ARG((c.a.n + KM_BM - 1) / KM_BM <= 65535 && c.kd->P % 2 == 0 && c.kd->parts[c.part_lo].poff % 2 == 0);
+  DFH_TRY(set_lds_limits(ctx));
+  const KmArgs a = km_args(c);
+  dim3 grid((unsigned)((c.b.n + 127) / 128), (unsigned)((c.a.n + KM_BM - 1) / KM_BM));
+  hipLaunchKernelGGL(kernmat_colw_kernel, grid, dim3(256), SM4, ctx->stream, a, c.col_w);
+  DFH_LAUNCH_CHECK();
   return DFH_OK;
 }

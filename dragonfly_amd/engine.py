@@ -302,6 +302,19 @@ class Engine(object):
   def empty(self, shape):
     return DeviceArray(self, shape)
 
+  def join_fixed(self, z, cands):
+    """ The joint candidates of a fixed fidelity (dfh_join_fixed_columns): row a of the result is [z, cands[a]], what
+        mfgp.get_ZX_from_ZZ_XX([z] * m, cands) builds on the host (opt/gpb_acquisitions.py:314-332), written in HBM.
+        cands: a DeviceArray [m x d] (a host array is uploaded first).  Returns a DeviceArray [m x (p + d)]. """
+    z = _f64(np.ravel(z))
+    if not isinstance(cands, DeviceArray):
+      cands = self.to_device(np.atleast_2d(_f64(cands)))
+    m, d = cands.shape
+    out = DeviceArray(self, (max(m, 1), len(z) + d))
+    out.shape, out.size = (m, len(z) + d), m * (len(z) + d)
+    check(self.lib.dfh_join_fixed_columns(self.ctx, _ptr(z), len(z), _ptr(cands), m, d, _ptr(out)))
+    return out
+
   def random_candidates(self, num, dim, bounds=None, rng=None, out=None, rows=None):
     """ `num` uniform points of the box `bounds` ([dim][2]; None = unit cube) generated in HBM:
         the draw np.random.random((num, dim)) mapped to the bounds (oper_utils.py:62,
@@ -874,6 +887,46 @@ class FittedGP(object):
     bi = np.empty(G, dtype=np.int64)
     vals = np.empty(int(ms.sum()), dtype=np.float64) if return_vals else None
     check(self.engine.lib.dfh_gp_add_ucb_all(self.handle, _ptr(be), _ptr(flat), _ptr(ms), _ptr(vals),
+                                             _ptr(bv), _ptr(bi)))
+    if return_vals:
+      return bv, bi, np.split(vals, np.cumsum(ms)[:-1])
+    return bv, bi
+
+  def mf_add_ucb_group(self, z_opt, group, beta, Xg, return_vals=False):
+    """ add_ucb_group for a multi-fidelity GP with an additive domain model at the fidelity z_opt
+        (dfh_mf_add_ucb_group; _mf_add_ucb_acq_j, opt/gpb_acquisitions.py:360-374).  `group` counts the groups of
+        the domain kernel, Xg holds that group's columns. """
+    z = _f64(np.ravel(z_opt))
+    Xg, m = self._rows(Xg)
+    vals = np.empty(m) if return_vals else None
+    bv = C.c_double(0)
+    bi = C.c_int64(-1)
+    check(self.engine.lib.dfh_mf_add_ucb_group(self.handle, _ptr(z), int(group), float(beta), _ptr(Xg), m,
+                                               _ptr(vals), C.byref(bv), C.byref(bi)))
+    if return_vals:
+      return bv.value, bi.value, vals
+    return bv.value, bi.value
+
+  def mf_add_ucb_all(self, z_opt, betas, cands_per_group, return_vals=False, sizes=None):
+    """ add_ucb_all for a multi-fidelity GP with an additive domain model at the fidelity z_opt
+        (dfh_mf_add_ucb_all): every group of the domain kernel in one device call, one posterior solve.
+        Arguments and results as add_ucb_all. """
+    z = _f64(np.ravel(z_opt))
+    if isinstance(cands_per_group, DeviceArray):
+      flat = cands_per_group
+      ms = np.ascontiguousarray(sizes, dtype=np.int64)
+    else:
+      blocks = [_f64(c) for c in cands_per_group]
+      ms = np.ascontiguousarray([b.shape[0] for b in blocks], dtype=np.int64)
+      flat = np.ascontiguousarray(np.concatenate([b.ravel() for b in blocks]), dtype=np.float64)
+    G = len(ms)
+    be = _f64(np.asarray(betas, dtype=float).reshape(-1))
+    if len(be) != G:
+      raise ValueError('mf_add_ucb_all: need one beta per group.')
+    bv = np.empty(G, dtype=np.float64)
+    bi = np.empty(G, dtype=np.int64)
+    vals = np.empty(int(ms.sum()), dtype=np.float64) if return_vals else None
+    check(self.engine.lib.dfh_mf_add_ucb_all(self.handle, _ptr(z), _ptr(be), _ptr(flat), _ptr(ms), _ptr(vals),
                                              _ptr(bv), _ptr(bi)))
     if return_vals:
       return bv, bi, np.split(vals, np.cumsum(ms)[:-1])

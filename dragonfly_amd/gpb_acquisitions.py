@@ -1,6 +1,7 @@
 """Acquisition functions for Bayesian optimisation on the MI355X -- host-side mirror of
 dragonfly/opt/gpb_acquisitions.py (UCB :215, PI :230, EI :251, TTEI :282, TS :119, add-UCB :139;
-hallucination wrappers :43-87; synchronous batches :90-115; namespaces asy / syn / seq :443-471).
+hallucination wrappers :43-87; synchronous batches :90-115; BOCA's view of a multi-fidelity GP, its add-UCB and
+its decision step :313-439; namespaces asy / syn / seq :443-471).
 
 Same callables, same `anc_data` fields (gp_bandit.py:462-484): `asy.<acq>(gp, anc_data) -> point`,
 `syn.<acq>(num_workers, gps, anc_datas) -> [points]`.
@@ -75,8 +76,80 @@ def _is_device_gp(gp):
 
 def _can_fuse(gp, anc_data):
   """ The fused candidates -> posterior -> acquisition -> arg-max call needs a device kernel; GPs
-      whose kernel the host evaluates take the reference's closure route (batched gp.eval). """
-  return _is_rand_euclidean(anc_data) and _is_device_gp(gp) and not getattr(anc_data, 'is_mf', False)
+      whose kernel the host evaluates take the reference's closure route (batched gp.eval).  In a
+      multi-fidelity run only BOCA's own view of a device GP (FidelToOptGP) is fused. """
+  if not _is_rand_euclidean(anc_data):
+    return False
+  if isinstance(gp, FidelToOptGP):
+    return gp.is_fusable()
+  return _is_device_gp(gp) and not getattr(anc_data, 'is_mf', False)
+
+
+class FidelToOptGP(object):
+  """ The GP BOCA hands the acquisitions: the multi-fidelity GP seen at fidel_to_opt
+      (_get_fidel_to_opt_gp, gpb_acquisitions.py:314-332) -- the reference Namespace's five attributes,
+      plus the GP and the fidelity themselves, so that the acquisitions can take the fused route: the
+      candidates drawn as ever, joined with the fidelity in HBM (Engine.join_fixed) and handed to the
+      joint GP's fused calls with the joint (fidelity, point) pairs in progress. """
+
+  def __init__(self, mfgp, fidel_to_opt):
+    self.mfgp, self.fidel_to_opt = mfgp, fidel_to_opt
+    self.kernel = mfgp.get_domain_kernel()
+
+  def _joint(self, x):
+    return self.mfgp.get_ZX_from_ZZ_XX([self.fidel_to_opt] * len(x), x)
+
+  def eval(self, x, *args, **kwargs):
+    return self.mfgp.eval_at_fidel([self.fidel_to_opt] * len(x), x, *args, **kwargs)
+
+  def eval_with_hallucinated_observations(self, x, halluc_fidel_pts, *args, **kwargs):
+    return self.mfgp.eval_with_hallucinated_observations(self._joint(x), halluc_fidel_pts, *args, **kwargs)
+
+  def draw_samples(self, n, x, *args, **kwargs):
+    return self.mfgp.draw_samples(n, self._joint(x), *args, **kwargs)
+
+  def draw_samples_with_hallucinated_observations(self, n, x, halluc_fidel_pts, *args, **kwargs):
+    return self.mfgp.draw_samples_with_hallucinated_observations(n, self._joint(x), halluc_fidel_pts, *args, **kwargs)
+
+  def is_fusable(self):
+    """ A Euclidean multi-fidelity mirror GP with a device kernel: its joint points are [z, x] rows. """
+    from .mf_gp import EuclideanMFGP
+    return isinstance(self.mfgp, EuclideanMFGP) and _is_device_gp(self.mfgp)
+
+  def fused_inputs(self, anc_data):
+    """ (candidates, joint candidates in HBM, prior-mean arguments, joint pairs in progress) of a fused call: the
+        candidates come from the global np.random state exactly as for a single-fidelity GP. """
+    engine = self.mfgp.device_gp.engine
+    if DEVICE_CANDIDATES:
+      bounds = np.asarray(anc_data.domain.bounds, dtype=np.float64)
+      cands = engine.random_candidates(int(anc_data.max_evals), len(bounds), bounds=bounds)
+    else:
+      cands = _candidates(anc_data)
+    joint = engine.join_fixed(self.fidel_to_opt, cands)
+    const = getattr(self.mfgp.mean_func, 'constant_value', None)
+    if const is not None:
+      mean = dict(mean_const=float(const))
+    else:
+      host = cands if isinstance(cands, np.ndarray) else cands.download()
+      mean = dict(mean_vals=self.mfgp.mean_func(self._joint(list(host))))
+    pts = _in_progress(anc_data)
+    return cands, joint, mean, (None if pts is None else _as_2d_array(pts))
+
+
+def _winning_row(cands, idx):
+  return cands[idx] if isinstance(cands, np.ndarray) else cands.row(idx)
+
+
+def _fused_argmax_at_fidel(view, acq, params, anc_data):
+  """ _fused_argmax for BOCA's view: the joint GP's fused call on [fidel_to_opt, candidate] rows; the
+      winner is read from the un-joined candidates. """
+  cands, joint, mean, Xh = view.fused_inputs(anc_data)
+  if gaplog.ENABLED:
+    _, idx, vals = view.mfgp.device_gp.acq_argmax(acq, joint, params=params, X_halluc=Xh, return_vals=True, **mean)
+    gaplog.top2('acq_argmax', vals)
+  else:
+    _, idx = view.mfgp.device_gp.acq_argmax(acq, joint, params=params, X_halluc=Xh, **mean)
+  return _winning_row(cands, idx)
 
 
 def _fortran_direct_available():
@@ -174,6 +247,8 @@ def get_gp_sampler_for_parallel_strategy(gp, anc_data):
 
 def _fused_argmax(gp, acq, params, anc_data):
   """ Candidates -> posterior -> acquisition -> arg-max on the device; returns the point. """
+  if isinstance(gp, FidelToOptGP):
+    return _fused_argmax_at_fidel(gp, acq, params, anc_data)
   Xh = _halluc_points(anc_data)
   if DEVICE_CANDIDATES:
     cands, mean = _device_candidates(gp, anc_data)
@@ -242,6 +317,8 @@ def asy_ts(gp, anc_data):
   if anc_data.acq_opt_method != 'rand':
     anc_data.max_evals *= 4
     anc_data.acq_opt_method = 'rand'
+  if isinstance(gp, FidelToOptGP) and _can_fuse(gp, anc_data):
+    return _ts_at_fidel(gp, anc_data)
   Xh = _halluc_points(anc_data)
   fused = anc_data.domain.get_type() == 'euclidean' and _is_device_gp(gp)
   if fused and Xh is not None:
@@ -269,6 +346,30 @@ def asy_ts(gp, anc_data):
     return cands[idx]
   _, idx = gp.device_gp.thompson(cands, normals, block=len(cands), mean_vals=gp.mean_func(cands), **halluc)
   return cands[idx]
+
+
+def _ts_at_fidel(view, anc_data):
+  """ asy_ts for BOCA's view: one joint draw over the [fidel_to_opt, candidate] rows on the device,
+      the joint pairs in progress hallucinated where the fitted handle can (FittedGP.fused_draws). """
+  pts = _in_progress(anc_data)
+  if pts is not None and not getattr(view.mfgp.device_gp, 'fused_draws', False):
+    return maximise_acquisition(get_gp_sampler_for_parallel_strategy(view, anc_data), anc_data, vectorised=True)
+  cands, joint, mean, Xh = view.fused_inputs(anc_data)
+  halluc = {} if Xh is None else {'X_halluc': Xh}
+  device_gp = view.mfgp.device_gp
+  m = joint.shape[0]
+  if DEVICE_CANDIDATES:
+    normals = device_gp.engine.random_normals(m)
+  else:
+    normals = np.random.normal(size=(m, 1)).ravel()
+  if gaplog.ENABLED:
+    _, idx, samples, _ = device_gp.thompson(joint, normals, block=m, return_samples=True, **mean, **halluc)
+    gaplog.top2('thompson', samples)
+  else:
+    _, idx = device_gp.thompson(joint, normals, block=m, **mean, **halluc)
+  if DEVICE_CANDIDATES:
+    normals.free()
+  return _winning_row(cands, idx)
 
 
 # Add-UCB -------------------------------------------------------------------------------------
@@ -401,6 +502,101 @@ def asy_rand(_, anc_data):
       maximiser's single call with all candidates still draws one, as in the reference). """
   vectorised = anc_data.acq_opt_method == 'rand'
   return maximise_acquisition(lambda x: np.random.random((1,) if vectorised else (len(x),)), anc_data)
+
+
+# Multi-fidelity strategies (gpb_acquisitions.py:313-439) ----------------------------------------
+def _get_fidel_to_opt_gp(mfgp, fidel_to_opt):
+  """ gpb_acquisitions.py:314-332 """
+  return FidelToOptGP(mfgp, fidel_to_opt)
+
+
+def _add_ucb_for_boca(mfgp, fidel_to_opt, mean_funcs, anc_data):
+  """ gpb_acquisitions.py:334-388: _add_ucb for a multi-fidelity GP with an additive domain model, at
+      fidel_to_opt.  Group j's cross matrix is kern_scale * k_fid(Z, fidel_to_opt) * k_j(x_j, X[:, group j]),
+      its prior variance kern_scale * k_fid(f2o, f2o) * k_j(x, x); L and alpha are the joint GP's and stay
+      in HBM (FittedGP.mf_add_ucb_group / _all).  The candidates are drawn as _add_ucb draws them. """
+  domain_kernel = mfgp.domain_kernel
+  groupings = domain_kernel.groupings
+  num_groups = len(domain_kernel.kernel_list)
+  all_bounds = np.asarray(anc_data.domain_bounds, dtype=np.float64)
+  per_group_evals = int(anc_data.max_evals // num_groups)
+  betas = [_get_add_ucb_beta_th(len(grp), anc_data.t) for grp in groupings]
+  point = np.zeros((sum(len(grp) for grp in groupings),))
+  device_gp = mfgp.device_gp
+  if mean_funcs is not None or not _is_rand_euclidean(anc_data):
+    if mean_funcs is None:
+      mean_funcs = lambda x: np.array([0] * len(x))
+    if not hasattr(mean_funcs, '__iter__'):
+      mean_funcs = [mean_funcs] * num_groups
+    for j, (grp, beta, mean_func_j) in enumerate(zip(groupings, betas, mean_funcs)):
+      def _mf_group_acq(X_j, _j=j, _beta=beta, _mean=mean_func_j):
+        X_j = _as_2d_array(X_j)
+        return device_gp.mf_add_ucb_group(fidel_to_opt, _j, _beta, X_j, return_vals=True)[2] + _mean(X_j)
+      anc_j = copy(anc_data)
+      anc_j.max_evals = per_group_evals
+      anc_j.domain = _BoxDomain(all_bounds[grp])
+      point[grp] = maximise_acquisition(_mf_group_acq, anc_j)
+    return point
+  if DEVICE_CANDIDATES:
+    engine = device_gp.engine
+    widths = [len(grp) for grp in groupings]
+    starts = np.concatenate([[0], np.cumsum([per_group_evals * w for w in widths])])
+    flat = engine.empty((int(starts[-1]),))
+    for grp, start in zip(groupings, starts):
+      engine.random_candidates(per_group_evals, len(grp), bounds=all_bounds[grp], out=flat.offset(start))
+    _, winners = device_gp.mf_add_ucb_all(fidel_to_opt, betas, flat, sizes=[per_group_evals] * num_groups)
+    for grp, start, idx in zip(groupings, starts, winners):
+      point[grp] = flat.slice(int(start) + int(idx) * len(grp), len(grp))
+    return point
+  cands = [map_to_bounds(np.random.random((per_group_evals, len(grp))), all_bounds[grp]) for grp in groupings]
+  _, winners = device_gp.mf_add_ucb_all(fidel_to_opt, betas, cands)
+  for grp, cands_g, idx in zip(groupings, cands, winners):
+    point[grp] = cands_g[int(idx)]
+  return point
+
+
+def asy_add_ucb_for_boca(mfgp, fidel_to_opt, anc_data):
+  """ gpb_acquisitions.py:390-392 """
+  return _add_ucb_for_boca(mfgp, fidel_to_opt, None, anc_data)
+
+
+def syn_add_ucb_for_boca(num_workers, list_of_mfgps, fidel_to_opt, anc_data):
+  """ gpb_acquisitions.py:394-397 """
+  # pylint: disable=unused-argument
+  raise NotImplementedError('Not Implemented Yet!')
+
+
+def boca(select_pt_func, mfgp, anc_data, func_caller):
+  """ BOCA's decision (gpb_acquisitions.py:399-439; Kandasamy et al. 2017): the next point by the
+      acquisition at fidel_to_opt -- fused on the device through FidelToOptGP, add-UCB through
+      mf_add_ucb_* -- then the fidelity: among the caller's candidate fidelities those whose posterior
+      standard deviation at the point (one eval_at_fidel call) exceeds the threshold, the cheapest of
+      them unless it costs more than boca_max_low_fidel_cost_ratio of fidel_to_opt. """
+  if anc_data.curr_acq == 'add_ucb':
+    next_eval_point = asy_add_ucb_for_boca(mfgp, func_caller.fidel_to_opt, anc_data)
+  else:
+    fidel_to_opt_gp = _get_fidel_to_opt_gp(mfgp, func_caller.fidel_to_opt)
+    next_eval_point = select_pt_func(fidel_to_opt_gp, anc_data)
+  candidate_fidels, cost_ratios = func_caller.get_candidate_fidels_and_cost_ratios(next_eval_point, filter_by_cost=True)
+  num_candidates = len(candidate_fidels)
+  cost_ratios = np.array(cost_ratios)
+  sqrt_cost_ratios = np.sqrt(cost_ratios)
+  information_gaps = np.array(func_caller.get_information_gap(candidate_fidels))
+  _, cand_fidel_stds = mfgp.eval_at_fidel(candidate_fidels, [next_eval_point] * num_candidates, uncert_form='std')
+  cand_fidel_stds = cand_fidel_stds / np.sqrt(mfgp.kernel.hyperparams['scale'])
+  std_thresholds = anc_data.boca_thresh_coeff * anc_data.y_range * sqrt_cost_ratios * information_gaps
+  high_std_idxs = cand_fidel_stds > std_thresholds
+  qualifying_idxs = np.where(high_std_idxs)[0]
+  if len(qualifying_idxs) == 0:
+    return func_caller.fidel_to_opt, next_eval_point
+  qualifying_fidels = [candidate_fidels[idx] for idx in qualifying_idxs]
+  qualifying_sqrt_cost_ratios = sqrt_cost_ratios[qualifying_idxs]
+  qualifying_cost_ratios = cost_ratios[qualifying_idxs]
+  next_eval_fidel_idx = qualifying_sqrt_cost_ratios.argmin()
+  # a qualifying fidelity that costs nearly as much as fidel_to_opt is not worth the detour
+  if qualifying_cost_ratios[next_eval_fidel_idx] > anc_data.boca_max_low_fidel_cost_ratio:
+    return func_caller.fidel_to_opt, next_eval_point
+  return qualifying_fidels[next_eval_fidel_idx], next_eval_point
 
 
 # Synchronous versions (gpb_acquisitions.py:129, 191, 225, 241, 263, 296, 308) -------------------

@@ -63,6 +63,12 @@ edited):
                K objectives' posteriors (or joint draws, points in progress hallucinated on the device), the
                scalarisation and the arg-max in one device call -- the reference's own callables elsewhere.
                Opt-in: without the flag the per-objective call stream of S4' stays exactly as it was.
+  S4''' BOCA   (only with install(multi_fidelity=True, boca=True)) dragonfly.opt.gpb_acquisitions.boca (looked up
+               at call time, opt/gp_bandit.py:495,660,663) -> a dispatcher: dragonfly_amd.gpb_acquisitions.boca when
+               the GP is the mirror EuclideanMFGP with a device kernel on a Euclidean domain -- the point chosen by
+               the fused call on [fidel_to_opt, candidate] rows joined in HBM (add-UCB: dfh_mf_add_ucb_all on the
+               joint GP's factor), the fidelity by the reference's rule over one eval_at_fidel call -- the
+               reference's own boca otherwise.  Opt-in: without the flag the call stream of S2' stays as it was.
 A compiled Fortran DIRECT, when present, keeps working: it calls gp.eval per point, which now
 runs on the device, through `external_maximise_with_method`.
 """
@@ -76,11 +82,15 @@ from . import gaplog
 _saved = []     # (object, attribute name, original value)
 
 
-def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, multi_objective=False, tuning_gpus=None):
+def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, multi_objective=False, tuning_gpus=None,
+            boca=False):
   """ Rebinds the names listed above; returns the list of patched attributes.
+      boca=True (only together with multi_fidelity=True; ValueError otherwise): BOCA's decision step runs on the device.
       tuning_gpus=N > 1 (with batched_tuning): a tuning batch large enough to fill more than one GPU
       (parallel.lml_shard_plan: more than 256 candidates up to n = 2047) is cut over N GPUs of this process
       (dfh_mgpu_lml_batch); every other batch, and everything with None or 1, goes exactly where it went before. """
+  if boca and not multi_fidelity:
+    raise ValueError('install(boca=True) needs multi_fidelity=True: BOCA runs on the device through the mirror MF GP.')
   import dragonfly.gp.kernel as ref_kernel
   import dragonfly.gp.euclidean_gp as ref_egp
   import dragonfly.opt.gpb_acquisitions as ref_acq
@@ -114,6 +124,8 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
       setattr(ref_ns, acq, _euclidean_dispatch(getattr(our_ns, acq), getattr(ref_ns, acq)))
       patched.append('dragonfly.opt.gpb_acquisitions.%s.%s' % (ns_name, acq))
   gpb_acquisitions.external_maximise_with_method = maximise_with_method
+  if boca:
+    _set(ref_acq, 'boca', _boca_dispatch(gpb_acquisitions.boca, ref_acq.boca))
   # the multi-objective acquisitions (opt/multiobjective_gpb_acquisitions.py:19-107) are closures
   # over rows of points handed to maximise_acquisition, a name they import at module level: with
   # ours they get the batched tree search / vectorised random search on Euclidean domains
@@ -164,6 +176,20 @@ def _euclidean_dispatch(ours, theirs):
   acquisition.__wrapped__ = ours
   acquisition.reference_callable = theirs
   return acquisition
+
+
+def _boca_dispatch(ours, theirs):
+  """ dragonfly.opt.gpb_acquisitions.boca under install(boca=True): ours for the mirror EuclideanMFGP with a device
+      kernel on a Euclidean domain, the reference's own boca for everything else. """
+  def boca(select_pt_func, mfgp, anc_data, func_caller):
+    from . import gpb_acquisitions, mf_gp
+    if anc_data.domain.get_type() == 'euclidean' and isinstance(mfgp, mf_gp.EuclideanMFGP) and \
+       gpb_acquisitions._is_device_gp(mfgp):     # pylint: disable=protected-access
+      return ours(select_pt_func, mfgp, anc_data, func_caller)
+    return theirs(select_pt_func, mfgp, anc_data, func_caller)
+  boca.__wrapped__ = ours
+  boca.reference_callable = theirs
+  return boca
 
 
 # DFH_SLICE_MERGE=0: the speculative slice sampler's stepping-out and shrinking candidates in separate density calls again

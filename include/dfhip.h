@@ -350,6 +350,32 @@ int dfh_gp_add_ucb_group(dfh_gp* gp, int32_t group, double beta, const double* X
 int dfh_gp_add_ucb_all(dfh_gp* gp, const double* betas, const double* Xg_all, const int64_t* m_per_group,
                        double* vals_out, double* best_vals, int64_t* best_idx);
 
+/* ---- BOCA's decision step on a multi-fidelity GP (opt/gpb_acquisitions.py:313-439) --------------------
+ * add-UCB at a fixed fidelity (_add_ucb_for_boca, :334-388).  The GP's kernel must be a PRODUCT of exactly two
+ * factors, the first a plain fidelity factor (SE | MATERN | EXPDECAY | POLY over the fidelity columns), the second a
+ * sum of SE / MATERN groups (factor_is_sum; the additive domain model, gp/euclidean_gp.py:696-707), and the GP must
+ * have been fitted without DFH_FIT_PROJECT_FIRST / DFH_FIT_TRY_BEFORE_PROJECT: DFH_ERR_BAD_ARG otherwise.  z_opt is
+ * fidel_to_opt ([number of fidelity columns], host or device).  `group` counts the groups of the additive factor,
+ * Xg holds that group's columns only.  With w_i = k_fid(z_opt, Z_i) and k_ff = k_fid(z_opt, z_opt) (:353-354):
+ *   K_tetr_j[a][i] = (kern_scale w_i) k_j(x_a, X_i[group j])                                   (:364-366)
+ *   mu_j = K_tetr_j alpha ; var_j = (kern_scale k_ff) k_j(x, x) - |L^-1 K_tetr_j^T|^2, not clipped (:367-373)
+ *   val = mu_j + beta sqrt(var_j)                                                              (:374)
+ * The additive factor's own scale does not enter (the reference uses the group kernels directly).  The weight
+ * multiplies the cross matrix where it is stored, so mean and solve read it weighted; the arg-max is np.argmax's
+ * (first NaN, else first maximum).  Outputs as dfh_gp_add_ucb_group / _all.                             */
+int dfh_mf_add_ucb_group(dfh_gp* gp, const double* z_opt, int32_t group, double beta,
+                         const double* Xg, int64_t m, double* vals_out, double* best_val, int64_t* best_idx);
+/* Every group of the additive factor in one call, one triangular solve with sum(m_g) right-hand sides (the loop
+ * of :357-381): layout of betas / Xg_all / m_per_group / vals_out / best_vals / best_idx as dfh_gp_add_ucb_all. */
+int dfh_mf_add_ucb_all(dfh_gp* gp, const double* z_opt, const double* betas, const double* Xg_all,
+                       const int64_t* m_per_group, double* vals_out, double* best_vals, int64_t* best_idx);
+/* The joint candidates of a fixed fidelity, mfgp.get_ZX_from_ZZ_XX([fidel_to_opt] * m, x) of _get_fidel_to_opt_gp
+ * (:314-332; gp/mf_gp.py get_ZX_from_ZZ_XX): out[a] = [z, Xd[a]], m x (p + d), written in HBM.  Xd [m x d] and out
+ * are DEVICE buffers, z [p] is a HOST buffer.  With it UCB / EI / PI / TTEI / TS at fidel_to_opt are
+ * dfh_gp_acq_argmax / dfh_gp_ts on joint points, with the joint in-progress pairs as Xh.                 */
+int dfh_join_fixed_columns(dfh_ctx* ctx, const double* z, int64_t p, const double* Xd, int64_t m, int64_t d,
+                           double* out);
+
 /* ---- multi-objective acquisitions (opt/multiobjective_gpb_acquisitions.py:19-107) -----------------
  * K fitted GPs -- one per objective: the same candidates, independent kernels and factors -- in ONE call:
  * candidates -> K posteriors (or K joint draws) -> scalarisation -> arg-max (np.argmax's: first NaN, else
