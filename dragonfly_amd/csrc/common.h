@@ -82,6 +82,9 @@ struct dfh_ctx {
   // the time-out of ~1 s on every fit
   int64_t chol_fallbacks = 0;
   int chol_fallback_streak = 0, chol_cooldown = 0;
+  // the kernel-matrix builder's booking (kernmat.h: KmRoute): the route the most recent call took and how many calls
+  // there were -- dfh_ctx_counters; the tests hold every case to the kernel it was written for with them
+  int64_t km_route = 0, km_dispatches = 0;
   LabelCache labels;               // labels of the last tuning call, resident (lml.hip: resident_labels)
   int lml_team_cooldown = 0;       // tuning batches that take one workgroup per candidate after a team's hand-off timed out
   hipEvent_t ev0 = nullptr, ev1 = nullptr;         // dfh_timer_begin / end

@@ -206,7 +206,10 @@ __device__ __forceinline__ double norm_pdf_dev(double x) {
   return exp(-(x * x) / 2.0) / 2.5066282746310002;   // scipy _norm_pdf: exp(-x**2/2.0)/sqrt(2*pi)
 }
 __device__ __forceinline__ double ei_norm_diff(double nd) {
-  return nd * ndtr_dev(nd) + norm_pdf_dev(nd);       // gpb_acquisitions.py:247-249
+  const double v = nd * ndtr_dev(nd) + norm_pdf_dev(nd);       // gpb_acquisitions.py:247-249
+  // z Phi + phi > 0 for every z.  Below z = -38 both terms are subnormal and their rounding can leave -2^-1074, where the
+  // reference (whose Phi has flushed to 0 there) returns phi >= 0: such a value is 0.  NaN stays NaN.
+  return v < 0.0 ? 0.0 : v;
 }
 
 }  // namespace

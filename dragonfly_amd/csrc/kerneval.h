@@ -28,7 +28,8 @@ __device__ __forceinline__ double ipow(double m, int k) {
 
 // exp(x) for the arguments a stationary kernel produces (x <= 0; also fine for moderate x > 0):
 // x = n ln2 + r, |r| <= ln2/2, degree-11 polynomial (Chebyshev-node interpolant of exp on that
-// interval: 4e-18 approximation error, ~0.7 ulp after Horner in fp64), scaled by v_ldexp_f64.
+// interval: 4e-18 approximation error; after Horner in fp64 and the reduction's rounding 1.2 ulp at worst, 1.6 ulp for
+// scale * exp -- measured per route against long double, profiles/kernel_value_ulps.json), scaled by v_ldexp_f64.
 // 17 fp64 VALU ops -- the epilogue of the kernel-matrix build is VALU-bound, so this is the lever.
 __device__ __forceinline__ double exp_fast(double x, const ExpConsts& ec) {
   const double n = rint(x * ec.log2e);
@@ -42,7 +43,8 @@ __device__ __forceinline__ double exp_fast(double x, const ExpConsts& ec) {
 }
 
 // exp(x) for x <= 0 without the exponent clamp of exp_fast: v_cvt_i32_f64 saturates, and v_ldexp_f64
-// with a hugely negative exponent returns 0 (what exp of such an x rounds to); NaN propagates
+// with a hugely negative exponent returns 0 (what exp of such an x rounds to); NaN propagates.  All three are held by
+// tests/test_gpu_kernel_values.py: squared distances beyond 1e10, the subnormal range to 2 ulp of 2^-1074, a NaN row.
 __device__ __forceinline__ double exp_fast_neg(double x, const ExpConsts& ec) {
   const double n = rint(x * ec.log2e);
   double r = fma(-n, ec.ln2_hi, x);

@@ -21,6 +21,13 @@ struct KmCall {
   const double* col_w = nullptr;   // (cross, one stationary part) K[a][i] = col_w[i] * k_part(a, i): the part alone, no outer scale
 };
 
+// The route a call took, as dfh_ctx_counters reports it (out[2]; 0: no call yet).  Booked on the host by the dispatcher;
+// km_launch_strip books KM_ROUTE_STRIP_MEAN where the posterior mean rode along.
+enum KmRoute {
+  KM_ROUTE_SYM = 1, KM_ROUTE_CROSS_LDS, KM_ROUTE_STRIP, KM_ROUTE_STRIP_MEAN, KM_ROUTE_SYMMULTI, KM_ROUTE_GENERIC, KM_ROUTE_ESP,
+  KM_ROUTE_COLW
+};
+
 // DFH_KM_* / DFH_PACK_FUSED, read once per process
 struct KmSwitches {
   int nt = env_int("DFH_KM_NT", -1);                        // streaming stores of kernmat_sym_kernel: < 0 = by size (km_args)

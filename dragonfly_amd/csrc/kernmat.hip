@@ -29,18 +29,24 @@ static int kernmat_dispatch(dfh_ctx* ctx, const KmCall& c) {
   if (c.mean) c.mean->done = false;
   if (c.a.n <= 0 || c.b.n <= 0) return DFH_OK;
   DFH_ARG(c.a.n < (1LL << 31) && c.b.n < (1LL << 31));
-  if (c.col_w) return km_launch_colw(ctx, c);      // weighted columns: one route knows them
-  if (c.kd->esp) {             // the whole ESP kernel in one kernel of its own; no fused posterior mean
-    DFH_ARG(c.part_lo == 0 && c.part_hi == c.kd->n_parts && c.apply_outer);
-    return km_launch_esp(ctx, c);
+  ctx->km_dispatches += 1;               // the booking of dfh_ctx_counters (host only)
+  KmRoute route;
+  if (c.col_w) route = KM_ROUTE_COLW;                    // weighted columns: one route knows them
+  else if (c.kd->esp) route = KM_ROUTE_ESP;              // the whole ESP kernel in one kernel of its own; no fused posterior mean
+  else if (km_single_aligned(c)) route = c.symmetric ? KM_ROUTE_SYM : (km_strip_ok(c) ? KM_ROUTE_STRIP : KM_ROUTE_CROSS_LDS);
+  else route = km_symmulti_ok(c) ? KM_ROUTE_SYMMULTI : KM_ROUTE_GENERIC;
+  ctx->km_route = route;
+  switch (route) {
+    case KM_ROUTE_COLW: return km_launch_colw(ctx, c);
+    case KM_ROUTE_ESP:
+      DFH_ARG(c.part_lo == 0 && c.part_hi == c.kd->n_parts && c.apply_outer);
+      return km_launch_esp(ctx, c);
+    case KM_ROUTE_SYM: return km_launch_sym(ctx, c);
+    case KM_ROUTE_STRIP: return km_launch_strip(ctx, c);      // books KM_ROUTE_STRIP_MEAN where the mean rides along
+    case KM_ROUTE_CROSS_LDS: return km_launch_cross_lds(ctx, c);
+    case KM_ROUTE_SYMMULTI: return km_launch_symmulti(ctx, c);
+    default: return km_launch_generic(ctx, c);
   }
-  if (km_single_aligned(c)) {
-    if (c.symmetric) return km_launch_sym(ctx, c);
-    if (km_strip_ok(c)) return km_launch_strip(ctx, c);
-    return km_launch_cross_lds(ctx, c);
-  }
-  if (km_symmulti_ok(c)) return km_launch_symmulti(ctx, c);
-  return km_launch_generic(ctx, c);
 }
 
 int kernmat_gram(dfh_ctx* ctx, const KernDev& kd, int part_lo, int part_hi, bool apply_outer, KmPts pts, double diag_add,

@@ -269,6 +269,7 @@ int km_launch_strip(dfh_ctx* ctx, const KmCall& c) {
     DFH_TRY(scratch_get(ctx, SCR_MUPART, (size_t)c.a.n * a.mu_nblk * 8, (void**)&a.mu_part));
     a.mu_alpha = c.mean->alpha; a.mu_out = c.mean->out;
     c.mean->done = true;
+    ctx->km_route = KM_ROUTE_STRIP_MEAN;
   }
   if (hp.kind == DFH_KERNEL_SE) {
     for (int i = 0; i < 12; ++i) a.ec.c[i] *= hp.scale_c;      // scale folded into the exp polynomial

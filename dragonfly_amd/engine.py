@@ -15,6 +15,8 @@ from ._lib import (ACQ_EI, ACQ_MEAN, ACQ_PI, ACQ_STD, ACQ_TTEI, ACQ_UCB, GET_ALP
                    check)
 
 MO_SCALARISATIONS = {'lin': _lib.MO_LIN, 'tch': _lib.MO_TCH}
+# dfh_ctx_counters out[2]: the route of the most recent kernel-matrix build (csrc/kernmat.h: KmRoute)
+KM_ROUTES = (None, 'sym', 'cross_lds', 'strip', 'strip_mean', 'symmulti', 'generic', 'esp', 'colw')
 ACQ_IDS = {'mean': ACQ_MEAN, 'ucb': ACQ_UCB, 'ei': ACQ_EI, 'pi': ACQ_PI, 'ttei': ACQ_TTEI,
            'std': ACQ_STD}
 
@@ -416,10 +418,12 @@ class Engine(object):
 
   def counters(self):
     """ {'chol_fallbacks': factorisations repeated on the hand-off-free schedule, 'chol_cooldown': how many
-        of the next ones skip the hand-off schedules} (dfh_ctx_counters) """
+        of the next ones skip the hand-off schedules, 'km_route': the route of the most recent kernel-matrix build
+        (KM_ROUTES; None before the first), 'km_dispatches': how many such builds there were} (dfh_ctx_counters) """
     arr = (C.c_int64 * 4)()
     check(self.lib.dfh_ctx_counters(self.ctx, arr))
-    return {'chol_fallbacks': int(arr[0]), 'chol_cooldown': int(arr[1])}
+    return {'chol_fallbacks': int(arr[0]), 'chol_cooldown': int(arr[1]), 'km_route': KM_ROUTES[int(arr[2])],
+            'km_dispatches': int(arr[3])}
 
   def gemm_profile(self, enable=True, fetch=True):
     """ Per-variant {launches, ms (sum of launch durations), flop, busy_ms (union of the launch

@@ -593,7 +593,10 @@ int dfh_ctx_timings(dfh_ctx* ctx, int enable, double* ms_out /* [DFH_T_COUNT] or
  * out[0] = factorisations repeated on the schedule without inter-workgroup hand-offs because a bounded
  * wait expired or a resident panel's block inverse was too poor (the result is the same, the call slower);
  * out[1] = how many of the next factorisations go straight to that schedule (set after two such repeats in
- * a row, e.g. on a device shared with other work); out[2..3] reserved (0).                          */
+ * a row, e.g. on a device shared with other work); out[2] = the route the most recent kernel-matrix build
+ * took (0 none yet, 1 symmetric single-part, 2 cross matrix through LDS, 3 strip, 4 strip with the posterior
+ * mean riding along, 5 symmetric multi-part, 6 generic, 7 ESP, 8 column-weighted); out[3] = how many such
+ * builds there were.  Both are kept on the host.                                                    */
 int dfh_ctx_counters(dfh_ctx* ctx, int64_t* out /* [4] */);
 
 /* Per-launch HIP-event timing of the fp64 MFMA GEMM kernel (the dominant kernel of the path),

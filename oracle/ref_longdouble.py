@@ -33,6 +33,8 @@ def _load():
                                      C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.ld_gaussian_draw.restype = C.c_int64
     lib.ld_gaussian_draw.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ld_acq_truth.restype = None
+    lib.ld_acq_truth.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.ld_set_threads.argtypes = [C.c_int]
     lib.ld_set_threads(min(32, os.cpu_count() or 1))
     _lib = lib
@@ -95,6 +97,15 @@ def kernel_matrix(kind, dim_bandwidths, scale, X1, X2, nu=0.0):
   lib.ld_kernel_matrix(0 if kind == 'se' else 1, float(nu), float(scale), _p(bw), _p(X1), X1.shape[0], _p(X2),
                        X2.shape[0], X1.shape[1], _p(K))
   return K
+
+
+def acq_truth(z):
+  """ (Phi(z), z Phi(z) + phi(z)) from erfcl / expl, each rounded to double """
+  lib = _load()
+  z = _f64(z).reshape(-1)
+  Phi, ei_norm = np.empty(len(z)), np.empty(len(z))
+  lib.ld_acq_truth(_p(z), len(z), _p(Phi), _p(ei_norm))
+  return Phi, ei_norm
 
 
 def gaussian_draw(mu, C_mat, u, jitter=0.0):
