@@ -15,6 +15,9 @@
 // LDS one k-pair ahead into a second register set, so every HBM/L2 and LDS latency hides under
 // the matrix pipe.  2 workgroups per CU (73.7 KB LDS, 250 VGPRs): the second wave per SIMD fills
 // the matrix pipe while the first sits at the barrier (measured: 1 workgroup per CU is ~10 % slower).
+// The plain kernels flip the wave priority inside the chunk -- 1 for the MFMA group behind the barrier, 0 for
+// the group in front of it -- so that of the two waves of a SIMD the one that has just left its barrier has
+// the pipe and the one about to wait gives way (+2 % at K >= 2048; see gemm_tile and docs/NOTES_gemm_kloop.md).
 //
 // MFMA f64 16x16x4 lane maps (cdna_hip_programming.md section 3):
 //   A operand : lane l holds A[i = l&15][k = l>>4]
@@ -129,8 +132,14 @@ __device__ __forceinline__ bool map_tile_lookahead(const GemmArgs& p, int la_pad
   return true;
 }
 
-template <bool TRANSB, bool EDGE, int WT, bool EXT>
-__device__ __forceinline__ void gemm_tile(const GemmArgs& p, int tm, int tn, bool is_la, int* la_cnt, double* smem) {
+// PRIO: the priority flips of the 128-tile K loop (plain kernels only: the factorisation's extended launches run
+// beside its latency-bound panel kernels and keep priority 0 throughout).
+// STAMP (diagnostics build only, gemm_f64_stamp_kernel below): s_memtime stamps around the pieces of the
+// 128-tile K loop, summed per wave into stamps[0..5]; every other instantiation compiles to the same code
+// with or without it.
+template <bool TRANSB, bool EDGE, int WT, bool EXT, bool PRIO = false, bool STAMP = false>
+__device__ __forceinline__ void gemm_tile(const GemmArgs& p, int tm, int tn, bool is_la, int* la_cnt, double* smem,
+                                          unsigned long long* stamps = nullptr) {
   using G = Geo<WT>;
   constexpr int BM = G::BM, BN = G::BN, BNP = G::BNP, TILE_A = G::TILE_A, TILE_B = G::TILE_B;
   constexpr int WS = WT * 16;                          // wave tile edge
@@ -256,7 +265,11 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& p, int tm, int tn, boo
   //   global loads of chunk c+1 | LDS reads of pair 1 (chunk c) | 32 MFMAs on pair 0 |
   //   LDS writes of chunk c+1, barrier | LDS reads of pair 0 (chunk c+1) | 32 MFMAs on pair 1
   // so every LDS read has a 32-MFMA (~2000 cycle) shadow and the only exposed work between the
-  // two MFMA groups is the store + barrier.
+  // two MFMA groups is the store + barrier: 13 % of a wave's chunk (stamped build, profiles/gemm_kloop_stamps.txt),
+  // next to nothing of it the wait for the global loads.  Moving the LDS writes up between the MFMAs of pair 0
+  // and the loads behind the barrier only empties that window into the barrier wait and gains nothing; what the
+  // window costs is decided by what the OTHER wave of the SIMD does meanwhile, hence PRIO: a wave runs the group
+  // behind its barrier at priority 1 and the group in front of it at priority 0.
   double fa[2][WT][2], fb[2][WT][2];
   auto read_frags = [&](int buf, int pair, int slot) {
     const double* as = As + buf * TILE_A + (wm * WS + l15) * BKP + l4 + pair * 8;
@@ -283,22 +296,61 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& p, int tm, int tn, boo
           acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[slot][i][ks], fb[slot][j][ks], acc[i][j], 0, 0, 0);
   };
 
+  // STAMP: time since the previous stamp goes to st_sum[slot].  (The stamp's value is waited for with
+  // lgkmcnt(0), so it sits only where the loop has no LDS access of its own in flight or waits for all anyway.)
+  [[maybe_unused]] unsigned long long st_last = 0, st_sum[5] = {0, 0, 0, 0, 0};
+  auto stamp = [&](int slot) {
+    if constexpr (STAMP) {
+      __builtin_amdgcn_sched_barrier(0);
+      const unsigned long long now = __builtin_amdgcn_s_memtime();
+      if (slot >= 0) st_sum[slot] += now - st_last;
+      st_last = now;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
   if (WT == 4) {
     if (nchunks > 0) read_frags(0, 0, 0);
+    stamp(-1);
     for (int kc = 0; kc < nchunks; ++kc) {
       const int buf = kc & 1;
       const bool more = kc + 1 < nchunks;
       if (more) load_chunk(kc + 1);
       read_frags(buf, 1, 1);
       __builtin_amdgcn_sched_barrier(0);
+      if (PRIO) __builtin_amdgcn_s_setprio(0);
       mfma_pair(0);
       __builtin_amdgcn_sched_barrier(0);
-      if (more) store_chunk(buf ^ 1);
-      __syncthreads();
+      if constexpr (STAMP) {
+        // __syncthreads() taken apart.  slot 0: loads out, LDS reads, group 0 | 1: what is left to wait of the
+        // global loads | 2: LDS writes retired | 3: the siblings have arrived | 4: LDS reads, group 1
+        stamp(0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        stamp(1);
+        if (more) store_chunk(buf ^ 1);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        stamp(2);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        stamp(3);
+      } else {
+        if (more) store_chunk(buf ^ 1);
+        __syncthreads();
+      }
       if (more) read_frags(buf ^ 1, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
+      if (PRIO) __builtin_amdgcn_s_setprio(1);
       mfma_pair(1);
       __builtin_amdgcn_sched_barrier(0);
+      stamp(4);
+    }
+    if (PRIO) __builtin_amdgcn_s_setprio(0);
+    if constexpr (STAMP) {
+      if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) stamps[q] = st_sum[q];
+        stamps[5] = (unsigned long long)nchunks;
+      }
     }
   } else {
     // small / latency-bound problems (64 x 64 tiles, few chunks): plain double-buffered loop
@@ -364,7 +416,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p) {
   if (WT == 2) __builtin_amdgcn_s_setprio(3);
   int tm, tn;
   map_tile(p, blockIdx.x, gridDim.x, tm, tn);
-  gemm_tile<TRANSB, EDGE, WT, false>(p, tm, tn, false, nullptr, smem);
+  gemm_tile<TRANSB, EDGE, WT, false, WT == 4>(p, tm, tn, false, nullptr, smem);
 }
 
 // look-ahead order: one tile per workgroup, exactly like the plain kernel but for the tile map and the
@@ -395,6 +447,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_cond_kernel(GemmArgs p, GemmE
     __syncthreads();                                   // the LDS images are free for the next tile
   }
 }
+
+#ifdef DFH_DEBUG_HOOKS
+// diagnostics: the plain NT 128-tile kernel, with or without its priority flips, with the K loop's stamps; out[(tile * 4 + wave) * 8 + 0..5]
+template <bool PRIO>
+__global__ __launch_bounds__(256, 2) void gemm_f64_stamp_kernel(GemmArgs p, unsigned long long* out) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  int tm, tn;
+  map_tile(p, blockIdx.x, gridDim.x, tm, tn);
+  gemm_tile<false, false, 4, false, PRIO, true>(p, tm, tn, false, nullptr, smem,
+                                          out + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8);
+}
+#endif
 
 template <bool TRANSB, bool EDGE, int WT, bool EXT = false>
 int launch(dfh_ctx* ctx, const GemmArgs& p, dim3 grid, const GemmExt* x = nullptr) {
@@ -749,3 +813,36 @@ extern "C" int dfh_ctx_gemm_profile(dfh_ctx* ctx, int enable, double* stats_out)
   }
   return DFH_OK;
 }
+
+#ifdef DFH_DEBUG_HOOKS      // diagnostics: built only with `python -m dragonfly_amd.build --debug-hooks` (include/dfhip_debug.h)
+extern "C" int dfh_debug_gemm_stamps(dfh_ctx* ctx, int64_t M, int64_t N, int64_t K, const double* A, const double* B,
+                                     double* Cd, int prio, double* out) {
+  DFH_ARG(ctx && A && B && Cd && out);
+  DFH_ARG(M > 0 && N > 0 && K > 0 && M % 128 == 0 && N % 128 == 0 && K % BK == 0 && M < (1LL << 30) && N < (1LL << 30));
+  GemmArgs p;
+  p.M = (int)M; p.N = (int)N; p.K = (int)K;
+  p.A = A; p.lda = K; p.B = B; p.ldb = K; p.Cin = Cd; p.ldcin = N; p.Cout = Cd; p.ldc = N;
+  p.sA = p.sB = p.sCin = p.sCout = p.sA2 = p.sB2 = p.sCin2 = p.sCout2 = 0;
+  p.cnt1 = 1; p.alpha = -1.0; p.beta = 1.0; p.flags = 0;
+  p.tiles_m = (int)(M / 128); p.tiles_n = (int)(N / 128);
+  const size_t ntiles = (size_t)p.tiles_m * p.tiles_n, nwaves = ntiles * 4;
+  unsigned long long* dev = nullptr;
+  DFH_HIP(hipMalloc(&dev, nwaves * 8 * sizeof(unsigned long long)));
+  DFH_HIP(hipMemsetAsync(dev, 0, nwaves * 8 * sizeof(unsigned long long), ctx->stream));
+  constexpr int smem = Geo<4>::SMEM_BYTES;
+  DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_stamp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+  DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_stamp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+  if (prio) hipLaunchKernelGGL(gemm_f64_stamp_kernel<true>, dim3((unsigned)ntiles), dim3(256), smem, ctx->stream, p, dev);
+  else hipLaunchKernelGGL(gemm_f64_stamp_kernel<false>, dim3((unsigned)ntiles), dim3(256), smem, ctx->stream, p, dev);
+  DFH_LAUNCH_CHECK();
+  std::vector<unsigned long long> host(nwaves * 8);
+  DFH_HIP(hipMemcpyAsync(host.data(), dev, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  DFH_HIP(hipStreamSynchronize(ctx->stream));
+  DFH_HIP(hipFree(dev));
+  for (int q = 0; q < 8; ++q) out[q] = 0.0;
+  for (size_t w = 0; w < nwaves; ++w)
+    for (int q = 0; q < 6; ++q) out[q] += (double)host[w * 8 + q];
+  out[6] = (double)nwaves;
+  return DFH_OK;
+}
+#endif  // DFH_DEBUG_HOOKS

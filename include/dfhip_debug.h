@@ -30,6 +30,13 @@ int dfh_debug_panel_data(double* A_out, double* Lfac_out);
  * ([workgroups][32 block columns][16] int64 of s_memrealtime, zeroed by the caller) from the next launch on;
  * NULL switches the stamps off (tools/dbg_lmlt.py).                                                        */
 int dfh_debug_lmlt_stamps(void* dev_buf);
+/* C -= A * B^T (A [M x K], B [N x K], C [M x N], device pointers, packed rows; M, N multiples of 128, K of 16) through the
+ * stamped instantiation of the 128-tile NT kernel, with (prio != 0) or without its priority flips: out[0..4] = s_memtime
+ * ticks (shader cycles), summed over all waves, spent in {loads out + LDS reads + MFMA group 0, what is left to wait of
+ * the global loads, LDS writes until retired, barrier, LDS reads + MFMA group 1}; out[5] = chunks summed over the waves;
+ * out[6] = waves (tools/dbg_gemm_stamps.py).                                                                            */
+int dfh_debug_gemm_stamps(dfh_ctx* ctx, int64_t M, int64_t N, int64_t K, const double* A, const double* B, double* C,
+                          int prio, double* out);
 #ifdef __cplusplus
 }
 #endif
