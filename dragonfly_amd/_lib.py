@@ -106,6 +106,8 @@ SIGNATURES = {
                           C.c_void_p, C.c_void_p, c_double_p, c_int64_p, c_int32_p]),
   'dfh_gp_draw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                             C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+  'dfh_gp_ts_pointwise': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,
+                                    C.c_void_p, C.c_void_p, c_double_p, c_int64_p]),
   'dfh_gp_add_ucb_group': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
                                      C.c_void_p, c_double_p, c_int64_p]),
   'dfh_mf_add_ucb_group': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,

@@ -1,5 +1,5 @@
-// The chunked posterior of a fitted GP and the acquisitions on it: predict, acquisition arg-max, add-UCB, covariance,
-// with the points in progress hallucinated (include/dfhip.h).
+// The chunked posterior of a fitted GP and the acquisitions on it: predict, acquisition arg-max, point-wise Thompson
+// sampling, add-UCB, covariance, with the points in progress hallucinated (include/dfhip.h).
 #include "gp.h"
 #include <limits.h>
 #include <algorithm>
@@ -489,6 +489,133 @@ extern "C" int dfh_gp_acq_argmax(dfh_gp* gp, int acq, const double* params, cons
   rq.want_var = acq != DFH_ACQ_MEAN;
   rq.vals_out = vals_out; rq.best_val = best_val; rq.best_idx = best_idx;
   return gp_eval_driver(gp, rq);
+}
+
+namespace {
+
+// Epilogue of one chunk of the point-wise Thompson sampling (dfh_gp_ts_pointwise): per candidate the one-point draw
+// s = sqrt(var) u + mu -- draw_gaussian_samples on a 1 x 1 covariance (general_utils.py:224-232: L.dot(U).T + mu, the
+// product and the sum rounded apart; the build has no implicit fusion) -- with var the unclipped posterior variance
+// of k_posterior_acq, and the first stage of the arg-max: one partial winner per workgroup (k_argmax_stage1's rule on
+// one element per thread; k_argmax_stage2 finishes).  *bad is set when some var is not > 0, where the 1 x 1
+// stable_cholesky fails on every rung of its ladder.
+__global__ __launch_bounds__(256) void k_ts_pointwise(double kxx, const double* __restrict__ kss, double mean_const,
+                                                      const double* __restrict__ mean_vals,
+                                                      const double* __restrict__ mu_raw, const double* __restrict__ ss,
+                                                      const double* __restrict__ ss2, const double* __restrict__ u, long m,
+                                                      long idx_base, double* __restrict__ samp, double* __restrict__ pv,
+                                                      long* __restrict__ pi, int* __restrict__ bad) {
+  __shared__ double sv[256];
+  __shared__ long si[256];
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  double bv = -INFINITY;
+  long bi = LONG_MAX;
+  int not_pd = 0;
+  if (i < m) {
+    const double mu = (mean_vals ? mean_vals[i] : mean_const) + mu_raw[i];   // gp_core.py:173-175
+    if (kss) kxx = kss[i];
+    const double var = ss2 ? kxx - (ss[i] + ss2[i]) : kxx - ss[i];           // gp_core.py:181 / :211, one point
+    not_pd = !(var > 0.0);                                                   // (NaN included)
+    bv = sqrt(var) * u[i] + mu;
+    bi = idx_base + i;
+    samp[i] = bv;
+  }
+  not_pd = __syncthreads_or(not_pd);
+  sv[threadIdx.x] = bv; si[threadIdx.x] = bi;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      const double ov = sv[threadIdx.x + s]; const long oi = si[threadIdx.x + s];
+      if (oi != LONG_MAX && (si[threadIdx.x] == LONG_MAX || better(ov, oi, sv[threadIdx.x], si[threadIdx.x]))) {
+        sv[threadIdx.x] = ov; si[threadIdx.x] = oi;
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    pv[blockIdx.x] = sv[0]; pi[blockIdx.x] = si[0];
+    if (not_pd) atomicOr(bad, 1);
+  }
+}
+
+}  // namespace
+
+// Point-wise Thompson sampling (include/dfhip.h): gp_eval_driver's chunk loop -- the posterior of dfh_gp_acq_argmax,
+// points in progress included -- with k_ts_pointwise as the epilogue.  One synchronisation per chunk: the chunk's
+// winner and its flag come back together.
+extern "C" int dfh_gp_ts_pointwise(dfh_gp* gp, const double* Xs, int64_t m, const double* Xh, int64_t q, const double* U,
+                                   double mean_const, const double* mean_vals, double* samples_out, double* best_val,
+                                   int64_t* best_idx) {
+  DFH_ARG(gp && Xs && U && m >= 1 && q >= 0 && (q == 0 || Xh));
+  DFH_ARG(!gp->gram);      // needs the kernel: this posterior was built from a Gram matrix
+  dfh_ctx* ctx = gp->ctx;
+  DFH_HIP(hipSetDevice(ctx->device));
+  HallucScope hs;                           // (hs.aug: the variance comes from the re-factored augmented GP)
+  DFH_TRY(halluc_resolve(gp, Xh, q, &hs));
+  const int64_t d = gp->d;
+  const int64_t mc_max = pick_chunk(ctx, gp->n + (hs.aug ? q : 0), m);
+  const ChunkStager stage(ctx, Xs, d, mean_vals);
+  double* vec = nullptr;
+  DFH_TRY(scratch_get(ctx, SCR_VEC, (size_t)mc_max * 8 * 6, (void**)&vec));
+  double* mu_raw = vec; double* ss = vec + mc_max; double* ss2 = vec + 2 * mc_max;
+  double* samp = vec + 3 * mc_max; double* mu_aug = vec + 4 * mc_max;
+  double* kss = gp->kd.stationary ? nullptr : vec + 5 * mc_max;
+  const int nblocks_max = (int)((mc_max + 255) / 256);
+  char* red = nullptr;                      // partial winners [nblocks] and the chunk's | their indices | the flag
+  DFH_TRY(scratch_get(ctx, SCR_RED, (size_t)(nblocks_max + 1) * 16 + 64, (void**)&red));
+  double* pv = reinterpret_cast<double*>(red);
+  long* pi = reinterpret_cast<long*>(red + (size_t)(nblocks_max + 1) * 8);
+  int* bad = reinterpret_cast<int*>(red + (size_t)(nblocks_max + 1) * 16);
+  Winner best;
+  ChunkReq creq;
+  for (int64_t i0 = 0; i0 < m; i0 += mc_max) {
+    const int64_t mc = std::min(mc_max, m - i0);
+    const double* xs_c = nullptr;
+    DFH_TRY(stage.xs(i0, mc, SCR_STAGE_A, &xs_c));
+    const double* mv_c = nullptr;
+    DFH_TRY(stage.mean(i0, mc, &mv_c));
+    const double* u_c = nullptr;
+    DFH_TRY(to_device(ctx, U + i0, (size_t)mc * 8, SCR_STAGE_C, &u_c));
+    ChunkOut co;
+    if (hs.aug) {
+      // mean from the real data, variance from the augmented factor (gp_core.py:195, 207-213)
+      creq.want_var = true; creq.h = nullptr;
+      DFH_TRY(posterior_chunk(hs.aug, xs_c, mc, d, creq, mu_aug, ss, ss2));
+      creq.want_var = false;
+      DFH_TRY(posterior_chunk(gp, xs_c, mc, d, creq, mu_raw, nullptr, nullptr, &co));
+    } else {
+      creq.want_var = true; creq.h = &hs.h;
+      DFH_TRY(posterior_chunk(gp, xs_c, mc, d, creq, mu_raw, ss, ss2, &co));
+    }
+    if (kss) DFH_TRY(prior_diag(ctx, gp->kd, co.Xsp, co.Nsp, mc, kss));
+    const int nblocks = (int)((mc + 255) / 256);
+    double hv = 0.0; long hi = -1; int hbad = 0;
+    {
+      SectionTimer t(ctx, DFH_T_ACQ);
+      DFH_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+      hipLaunchKernelGGL(k_ts_pointwise, dim3((unsigned)nblocks), dim3(256), 0, ctx->stream, gp->kd.kxx, (const double*)kss,
+                         mean_const, mv_c, (const double*)mu_raw, (const double*)ss,
+                         hs.block_q() > 0 ? (const double*)ss2 : (const double*)nullptr, u_c, (long)mc, (long)i0, samp, pv, pi, bad);
+      DFH_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_argmax_stage2, dim3(1), dim3(256), 0, ctx->stream, (const double*)pv, (const long*)pi, nblocks,
+                         pv + nblocks_max, pi + nblocks_max);
+      DFH_LAUNCH_CHECK();
+      DFH_HIP(hipMemcpyAsync(&hv, pv + nblocks_max, 8, hipMemcpyDeviceToHost, ctx->stream));
+      DFH_HIP(hipMemcpyAsync(&hi, pi + nblocks_max, 8, hipMemcpyDeviceToHost, ctx->stream));
+      DFH_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+      DFH_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if (hbad) {
+      dfh_set_error("Could not compute Cholesky decomposition of a candidate's 1 x 1 posterior covariance: the variance is "
+                    "not positive. This is likely because the M is not positive semi-definite or has infinities/nans.");
+      return DFH_ERR_JITTER;
+    }
+    best.merge(hv, (int64_t)hi);
+    if (samples_out) DFH_TRY(from_device(ctx, samples_out + i0, samp, (size_t)mc * 8));
+  }
+  DFH_HIP(hipStreamSynchronize(ctx->stream));
+  best.store(best_val, best_idx);
+  return DFH_OK;
 }
 
 extern "C" int dfh_gp_add_ucb_group(dfh_gp* gp, int32_t group, double beta, const double* Xg, int64_t m,

@@ -861,6 +861,33 @@ class FittedGP(object):
       return bv.value, bi.value, samples, [None if j == INT32_MIN else j for j in jps]
     return bv.value, bi.value
 
+  def thompson_pointwise(self, Xs, normals=None, X_halluc=None, mean_const=0.0, mean_vals=None, return_samples=False):
+    """ Point-wise Thompson sampling (dfh_gp_ts_pointwise): per candidate the one-point draw gp.draw_samples(1, [x]) --
+        with X_halluc gp.draw_samples_with_hallucinated_observations(1, [x], X_halluc) -- what the reference's
+        maximisers on Cartesian-product domains make of a sampler, in one device call.  normals: the m standard
+        normals (host array or DeviceArray); None: Engine.random_normals(m), which continues the global np.random
+        stream exactly as m calls of np.random.normal(size=(1, 1)) do.  A candidate whose variance is not positive
+        raises the ValueError of an exhausted jitter ladder.  Returns (best_val, best_idx[, samples]). """
+    Xs, m = self._rows(Xs)
+    own = normals is None
+    Uh = self.engine.random_normals(m) if own else (normals if isinstance(normals, DeviceArray) else _f64(np.ravel(normals)))
+    if Uh.size != m:
+      raise ValueError('normals must hold one standard normal per candidate.')
+    samples = np.empty(m) if return_samples else None
+    mv = None if mean_vals is None else (mean_vals if isinstance(mean_vals, DeviceArray) else _f64(mean_vals))
+    Xh, q = (None, 0) if X_halluc is None or len(X_halluc) == 0 else self._rows(X_halluc)
+    bv = C.c_double(0)
+    bi = C.c_int64(-1)
+    try:
+      check(self.engine.lib.dfh_gp_ts_pointwise(self.handle, _ptr(Xs), m, _ptr(Xh), q, _ptr(Uh), float(mean_const),
+                                                _ptr(mv), _ptr(samples), C.byref(bv), C.byref(bi)))
+    finally:
+      if own:
+        Uh.free()
+    if return_samples:
+      return bv.value, bi.value, samples
+    return bv.value, bi.value
+
   def add_ucb_group(self, group, beta, Xg, return_vals=False):
     Xg, m = self._rows(Xg)
     vals = np.empty(m) if return_vals else None

@@ -14,6 +14,12 @@ comes back.  Other acq_opt_method values are per-point serial tree searches in t
 (DIRECT / PDOO, out of scope): they are served through Dragonfly's own maximisers when this
 package is installed under Dragonfly (dragonfly_amd.install), each callback hitting GP.eval on
 the device.
+
+On a Cartesian-product domain the reference evaluates every acquisition one point per call.  Where
+cp_acquisition_applies holds -- the device CP GP on the kernel's descriptor, install(cp_acquisitions=True) -- a 'rand'
+step is the reference's own samples, packed in one pass, in ONE acq_argmax or (Thompson sampling: a one-point draw per
+candidate, not a joint draw) ONE thompson_pointwise call, and the tree search of an all-Euclidean product fetches its
+values a frontier per call.
 """
 import os
 from argparse import Namespace
@@ -171,8 +177,10 @@ def maximise_acquisition(acq_fn, anc_data, *args, **kwargs):
       reference visits but fetches the values a frontier per device call.  Anything else goes to
       Dragonfly's own maximiser when installed under it. """
   acq_opt_method = str(anc_data.acq_opt_method).lower()
+  if anc_data.domain.get_type() == 'cartesian_product':
+    return _maximise_acquisition_on_cp_domain(acq_fn, anc_data, *args, **kwargs)
   if anc_data.domain.get_type() != 'euclidean':
-    raise NotImplementedError('dragonfly_amd acquisitions handle Euclidean domains.')
+    raise NotImplementedError('dragonfly_amd acquisitions handle Euclidean and Cartesian-product domains.')
   if acq_opt_method.startswith('rand'):
     kwargs.pop('vectorised', None)
     _, opt_pt, _ = random_maximise(acq_fn, anc_data.domain.bounds, anc_data.max_evals)
@@ -191,6 +199,140 @@ def maximise_acquisition(acq_fn, anc_data, *args, **kwargs):
   _, opt_pt = external_maximise_with_method(anc_data.acq_opt_method, acquisition, anc_data.domain,
                                             anc_data.max_evals, *args, **kwargs)
   return opt_pt
+
+
+# Cartesian-product domains ------------------------------------------------------------------------
+def _cp_maximiser(anc_data):
+  """ How an acquisition is maximised on a Cartesian-product domain, by the reference's own tests of the method's name
+      (exd_utils.py:277-339): 'rand' -- its loop over random samples, here one vectorised call -- 'tree' -- PDOO, and
+      DIRECT where the Fortran library is not built, over the flattened bounds of a domain whose parts are all
+      Euclidean and that has no constraints (exd_utils.py:219-244), here a frontier per call -- or None: the GA, a
+      compiled DIRECT and everything else stay with the reference's maximiser. """
+  method = str(anc_data.acq_opt_method).lower()
+  if method == 'rand':
+    return 'rand'
+  if method.startswith('pdoo') or (method.startswith('direct') and not _fortran_direct_available()):
+    domain = anc_data.domain
+    if all(dom.get_type() == 'euclidean' for dom in domain.list_of_domains) and \
+       not getattr(domain, 'has_constraints', lambda: False)():
+      return 'tree'
+  return None
+
+
+def _cp_candidates(anc_data):
+  """ The random samples of _rand_maximise_vectorised_objective_in_cp_domain (exd_utils.py:252-263), by the
+      reference's own sampler and loop: its consumption of the global np.random state, its handling of constraints,
+      and its sample count, which may exceed max_evals. """
+  from dragonfly.exd.exd_utils import sample_from_cp_domain
+  domain, max_evals = anc_data.domain, anc_data.max_evals
+  rand_samples = []
+  num_sample_tries = 0
+  while not (len(rand_samples) >= max_evals or (len(rand_samples) > 0 and num_sample_tries >= 5)):
+    rand_samples.extend(sample_from_cp_domain(domain, int(max_evals), verbose_constraint_satisfaction=False))
+    num_sample_tries += 1
+    if len(rand_samples) == 0 and num_sample_tries % 10 == 0:
+      from warnings import warn
+      warn(('Sampling from domain failed despite %d attempts -- will continue trying but consider '
+            'reparametrising your domain if this problem persists.') % (num_sample_tries))
+  return rand_samples
+
+
+def _cp_flat_bounds(domain):
+  """ The flattened box of a product of Euclidean domains and the map from its rows back to points (lists of
+      per-part slices), exd_utils.py:223-232. """
+  dims = [dom.dim for dom in domain.list_of_domains]
+  starts = [0] + list(np.cumsum(dims))[:-1]
+  bounds = np.array([row for dom in domain.list_of_domains for row in dom.bounds], dtype=np.float64)
+  return bounds, lambda pt: [pt[cd:cd + d] for (cd, d) in zip(starts, dims)]
+
+
+def _maximise_acquisition_on_cp_domain(acq_fn, anc_data, *args, **kwargs):
+  """ maximise_acquisition for an acquisition over lists of Cartesian-product points ([m points] -> [m]): the random
+      samples in one call, the tree search a frontier per call; what the reference evaluates one point per callback
+      (gpb_acquisitions.py:35-37, exd_utils.py:265).  vectorised=True marks a sampler (asy_ts): a call of it on many
+      points is a joint draw, which the reference never makes on these domains, so it keeps one call per point.
+      Other maximisers are Dragonfly's own, point by point. """
+  route = _cp_maximiser(anc_data)
+  per_point = kwargs.pop('vectorised', False)
+  if route == 'rand':
+    cands = _cp_candidates(anc_data)
+    vals = [acq_fn([x]) for x in cands] if per_point else acq_fn(cands)
+    return cands[int(np.argmax(vals))]
+  if route == 'tree':
+    bounds, regroup = _cp_flat_bounds(anc_data.domain)
+    frontier = int(getattr(anc_data, 'pdoo_frontier', PDOO_FRONTIER))
+    _, opt_pt, _ = pdoo_maximise_batched(lambda rows: acq_fn([regroup(row) for row in rows]), bounds, anc_data.max_evals,
+                                         frontier=frontier, depth=2 if frontier > 0 else 0)
+    return regroup(opt_pt)
+  if external_maximise_with_method is None:
+    raise NotImplementedError(
+        'acq_opt_method=%s on a Cartesian-product domain is served by Dragonfly\'s own maximiser; install under '
+        'Dragonfly (dragonfly_amd.install) to use it.' % (anc_data.acq_opt_method))
+  _, opt_pt = external_maximise_with_method(anc_data.acq_opt_method, lambda x: acq_fn([x]), anc_data.domain,
+                                            anc_data.max_evals, *args, **kwargs)
+  return opt_pt
+
+
+def _is_cp_device_step(gp, anc_data):
+  """ A step on a Cartesian-product domain whose GP is the device GP running from the kernel's descriptor, with a
+      kernel guaranteed positive semi-definite (so the reference does not project the per-point covariances,
+      gp_core.py:849-857), in a run that is not multi-fidelity. """
+  return anc_data.domain.get_type() == 'cartesian_product' and not getattr(anc_data, 'is_mf', False) and \
+         _is_device_gp(gp) and hasattr(gp.kernel, 'pack_many') and gp.kernel.is_guaranteed_psd()
+
+
+def cp_acquisition_applies(acq, gp, anc_data):
+  """ Whether acquisition `acq` ('ucb' | 'ei' | 'pi' | 'ttei' | 'ts') of this module serves a step on a Cartesian-product
+      domain: _is_cp_device_step, and the maximiser is one of _cp_maximiser's two (Thompson sampling always takes
+      'rand', gpb_acquisitions.py:119-127).  install(cp_acquisitions=True) asks before it calls ours. """
+  if acq not in ('ucb', 'ei', 'pi', 'ttei', 'ts') or not _is_cp_device_step(gp, anc_data):
+    return False
+  return acq == 'ts' or _cp_maximiser(anc_data) is not None
+
+
+def _is_cp_rand(gp, anc_data):
+  """ A step the fused calls take on packed Cartesian-product candidates. """
+  return _is_cp_device_step(gp, anc_data) and _cp_maximiser(anc_data) == 'rand'
+
+
+def _cp_fused_inputs(gp, anc_data):
+  """ (candidates, the same packed into the descriptor's dense layout in one pass, prior-mean arguments, packed points
+      in progress or None) of a fused call on a Cartesian-product domain. """
+  cands = _cp_candidates(anc_data)
+  packed = gp.kernel.pack_many(cands)
+  const = getattr(gp.mean_func, 'constant_value', None)
+  mean = dict(mean_const=float(const)) if const is not None else dict(mean_vals=gp.mean_func(cands))
+  pts = _in_progress(anc_data)
+  return cands, packed, mean, (None if pts is None else gp.kernel.pack_many(pts))
+
+
+def _cp_fused_argmax(gp, acq, params, anc_data):
+  """ _fused_argmax on a Cartesian-product domain: the reference's samples, packed, in ONE acq_argmax; the point
+      returned is the winning sample object itself. """
+  cands, packed, mean, Xh = _cp_fused_inputs(gp, anc_data)
+  if gaplog.ENABLED:
+    _, idx, vals = gp.device_gp.acq_argmax(acq, packed, params=params, X_halluc=Xh, return_vals=True, **mean)
+    gaplog.top2('acq_argmax', vals)
+  else:
+    _, idx = gp.device_gp.acq_argmax(acq, packed, params=params, X_halluc=Xh, **mean)
+  return cands[idx]
+
+
+def _cp_thompson(gp, anc_data):
+  """ asy_ts on a Cartesian-product domain.  The reference draws the samples of the domain, then calls the sampler on
+      one point at a time: per candidate a one-point posterior, its 1 x 1 stable_cholesky and one
+      np.random.normal(size=(1, 1)) -- no joint draw.  Here: the same samples, then the m normals in the same order
+      (generated in HBM where the engine can, the global state left where m such calls leave it), and ONE
+      thompson_pointwise. """
+  cands, packed, mean, Xh = _cp_fused_inputs(gp, anc_data)
+  on_device = DEVICE_CANDIDATES and getattr(gp.device_gp.engine, 'random_normals', None) is not None
+  normals = None if on_device else np.random.normal(size=(len(cands), 1)).ravel()
+  if gaplog.ENABLED:
+    _, idx, samples = gp.device_gp.thompson_pointwise(packed, normals, X_halluc=Xh, return_samples=True, **mean)
+    gaplog.top2('thompson', samples)
+  else:
+    _, idx = gp.device_gp.thompson_pointwise(packed, normals, X_halluc=Xh, **mean)
+  return cands[idx]
 
 
 class _BoxDomain(object):
@@ -222,16 +364,21 @@ def _in_progress(anc_data):
 def _halluc_points(anc_data):
   """ The in-progress points as an array for the device calls (single-fidelity GPs only). """
   pts = _in_progress(anc_data)
-  if pts is None or getattr(anc_data, 'is_mf', False):
+  if pts is None or _points_stay_lists(anc_data):
     return None
   return _as_2d_array(pts)
+
+
+def _points_stay_lists(anc_data):
+  """ (fidelity, point) pairs and the points of a Cartesian-product domain are not rows of one matrix: the GP packs them """
+  return getattr(anc_data, 'is_mf', False) or anc_data.domain.get_type() == 'cartesian_product'
 
 
 def _get_gp_eval_for_parallel_strategy(gp, anc_data, uncert_form='std'):
   """ gpb_acquisitions.py:43-64 """
   pts = _in_progress(anc_data)
   if pts is not None:
-    pts = pts if getattr(anc_data, 'is_mf', False) else _as_2d_array(pts)
+    pts = pts if _points_stay_lists(anc_data) else _as_2d_array(pts)
     return lambda x: gp.eval_with_hallucinated_observations(x, pts, uncert_form=uncert_form)
   return lambda x: gp.eval(x, uncert_form=uncert_form)
 
@@ -240,7 +387,7 @@ def get_gp_sampler_for_parallel_strategy(gp, anc_data):
   """ gpb_acquisitions.py:67-87 """
   pts = _in_progress(anc_data)
   if pts is not None:
-    pts = pts if getattr(anc_data, 'is_mf', False) else _as_2d_array(pts)
+    pts = pts if _points_stay_lists(anc_data) else _as_2d_array(pts)
     return lambda x: gp.draw_samples_with_hallucinated_observations(1, x, pts).ravel()
   return lambda x: gp.draw_samples(1, x).ravel()
 
@@ -295,6 +442,8 @@ def _acquire(gp, anc_data, acq, params, formula):
   """ One acquisition step: fused on the device when possible, the closure route otherwise. """
   if _can_fuse(gp, anc_data):
     return _fused_argmax(gp, acq, params, anc_data)
+  if _is_cp_rand(gp, anc_data):
+    return _cp_fused_argmax(gp, acq, params, anc_data)
   return _host_acquisition(gp, anc_data, formula)
 
 
@@ -319,6 +468,8 @@ def asy_ts(gp, anc_data):
     anc_data.acq_opt_method = 'rand'
   if isinstance(gp, FidelToOptGP) and _can_fuse(gp, anc_data):
     return _ts_at_fidel(gp, anc_data)
+  if _is_cp_rand(gp, anc_data) and hasattr(gp.device_gp, 'thompson_pointwise'):
+    return _cp_thompson(gp, anc_data)
   Xh = _halluc_points(anc_data)
   fused = anc_data.domain.get_type() == 'euclidean' and _is_device_gp(gp)
   if fused and Xh is not None:
@@ -475,6 +626,8 @@ def _ttei(gp_eval, anc_data, ref_point, gp=None):
   ref_mean, ref_std = [float(np.ravel(v)[0]) for v in gp_eval([ref_point])]
   if gp is not None and _can_fuse(gp, anc_data):
     return _fused_argmax(gp, 'ttei', (ref_mean, ref_std), anc_data)
+  if gp is not None and _is_cp_rand(gp, anc_data):
+    return _cp_fused_argmax(gp, 'ttei', (ref_mean, ref_std), anc_data)
   def _tt_ei_acq(x):
     mu, sigma = gp_eval(x)
     comb_std = np.sqrt(ref_std ** 2 + sigma ** 2)

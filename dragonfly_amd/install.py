@@ -69,6 +69,12 @@ edited):
                the fused call on [fidel_to_opt, candidate] rows joined in HBM (add-UCB: dfh_mf_add_ucb_all on the
                joint GP's factor), the fidelity by the reference's rule over one eval_at_fidel call -- the
                reference's own boca otherwise.  Opt-in: without the flag the call stream of S2' stays as it was.
+  S4-CP        (only with install(cartesian_product=True, cp_acquisitions=True)) the S4 dispatchers of ucb / ei / pi / ttei / ts
+               call ours on Cartesian-product domains as well, when gpb_acquisitions.cp_acquisition_applies holds: the device
+               CP GP on the descriptor route, a kernel guaranteed PSD, no multi-fidelity, and 'rand' -- the reference's own
+               samples packed in one pass into ONE acq_argmax / thompson_pointwise call -- or the tree search on an
+               all-Euclidean product without constraints, a frontier per call.  The GA, a compiled DIRECT, add_ucb and
+               everything else keep the reference's callable.  Opt-in: the names rebound are the same either way.
 A compiled Fortran DIRECT, when present, keeps working: it calls gp.eval per point, which now
 runs on the device, through `external_maximise_with_method`.
 """
@@ -83,14 +89,19 @@ _saved = []     # (object, attribute name, original value)
 
 
 def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, multi_objective=False, tuning_gpus=None,
-            boca=False):
+            boca=False, cp_acquisitions=False):
   """ Rebinds the names listed above; returns the list of patched attributes.
       boca=True (only together with multi_fidelity=True; ValueError otherwise): BOCA's decision step runs on the device.
+      cp_acquisitions=True (only together with cartesian_product=True; ValueError otherwise): the S4 dispatchers call
+      ours on Cartesian-product domains too, where gpb_acquisitions.cp_acquisition_applies says so.  The names
+      rebound are the same with and without it.
       tuning_gpus=N > 1 (with batched_tuning): a tuning batch large enough to fill more than one GPU
       (parallel.lml_shard_plan: more than 256 candidates up to n = 2047) is cut over N GPUs of this process
       (dfh_mgpu_lml_batch); every other batch, and everything with None or 1, goes exactly where it went before. """
   if boca and not multi_fidelity:
     raise ValueError('install(boca=True) needs multi_fidelity=True: BOCA runs on the device through the mirror MF GP.')
+  if cp_acquisitions and not cartesian_product:
+    raise ValueError('install(cp_acquisitions=True) needs cartesian_product=True: the fused calls run on the device CP GP.')
   import dragonfly.gp.kernel as ref_kernel
   import dragonfly.gp.euclidean_gp as ref_egp
   import dragonfly.opt.gpb_acquisitions as ref_acq
@@ -121,7 +132,8 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
     our_ns = getattr(gpb_acquisitions, ns_name)
     for acq in ('ucb', 'ei', 'pi', 'ttei', 'ts', 'add_ucb'):
       _saved.append((ref_ns, acq, getattr(ref_ns, acq)))
-      setattr(ref_ns, acq, _euclidean_dispatch(getattr(our_ns, acq), getattr(ref_ns, acq)))
+      setattr(ref_ns, acq, _euclidean_dispatch(getattr(our_ns, acq), getattr(ref_ns, acq),
+                                               cp_acq=acq if cp_acquisitions else None))
       patched.append('dragonfly.opt.gpb_acquisitions.%s.%s' % (ns_name, acq))
   gpb_acquisitions.external_maximise_with_method = maximise_with_method
   if boca:
@@ -161,17 +173,27 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
   return patched
 
 
-def _euclidean_dispatch(ours, theirs):
+def _euclidean_dispatch(ours, theirs, cp_acq=None):
   """ The acquisition entry installed in the reference's namespaces: ours on Euclidean domains,
       the reference's own callable on every other domain (Cartesian-product, neural-network, ...
       domains keep running exactly as before).  Works for asy (gp, anc_data) and syn
-      (num_workers, gps, anc_datas) signatures: the ancillary data is the last argument. """
+      (num_workers, gps, anc_datas) signatures: the ancillary data is the last argument.
+      cp_acq (install(cp_acquisitions=True): the acquisition's name): ours on a Cartesian-product domain as well,
+      when gpb_acquisitions.cp_acquisition_applies holds for every GP of the call -- the device CP GP on the
+      descriptor route with a kernel guaranteed PSD, no multi-fidelity, 'rand' or the tree search; the GA, a compiled
+      DIRECT, host-kernel GPs and add-UCB stay with the reference's callable. """
   def acquisition(*args, **kwargs):
     anc_data = args[-1]
     if isinstance(anc_data, (list, tuple)):
       anc_data = anc_data[0]
     if anc_data.domain.get_type() == 'euclidean':
       return ours(*args, **kwargs)
+    if cp_acq is not None and anc_data.domain.get_type() == 'cartesian_product':
+      from .gpb_acquisitions import cp_acquisition_applies
+      gps = args[-2]
+      gps = list(gps) if isinstance(gps, (list, tuple)) else [gps]
+      if all(cp_acquisition_applies(cp_acq, gp, anc_data) for gp in gps):
+        return ours(*args, **kwargs)
     return theirs(*args, **kwargs)
   acquisition.__wrapped__ = ours
   acquisition.reference_callable = theirs

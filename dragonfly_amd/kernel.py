@@ -626,6 +626,33 @@ class CategoryCoder(object):
         out[i, c] = code
     return out
 
+  def encode_many(self, part_points):
+    """ encode() for many points at once: per column the distinct items are coded in order of first appearance
+        -- the codes encode() would give them going down the rows -- and the column is mapped through the
+        dictionary in one pass, with no Python statement per item.  Same codes, same dictionaries afterwards,
+        same errors. """
+    rows = np.array([list(pt) for pt in part_points], dtype=object)
+    if rows.ndim != 2:
+      raise ValueError('The points of a discrete part must all have the same number of items.')
+    n, dim = rows.shape
+    while len(self.columns) < dim:
+      self.columns.append({})
+    out = np.empty((n, dim), dtype=np.float64)
+    for c in range(dim):
+      codes = self.columns[c]
+      items = rows[:, c].tolist()
+      try:
+        for item in dict.fromkeys(items):
+          if not item == item:
+            raise ValueError('An item that is not equal to itself has no category code: %r.' % (item,))
+          if item not in codes:
+            codes[item] = len(codes)
+      except TypeError:
+        bad = next(it for it in items if getattr(it, '__hash__', None) is None)
+        raise ValueError('An unhashable item has no category code: %r.' % (bad,))
+      out[:, c] = np.fromiter(map(codes.__getitem__, items), dtype=np.float64, count=n)
+    return out
+
 
 class HammingKernel(Kernel):
   """ The Hamming kernel sum_c w_c [x_c == y_c] on lists of categories (kernel.py:436-457).  A call on lists of
@@ -656,6 +683,10 @@ class HammingKernel(Kernel):
   def pack(self, X):
     """ The points' category codes as the n x dim matrix the device compares. """
     return self.coder.encode(X)
+
+  def pack_many(self, X):
+    """ pack() of many points (the candidates of an acquisition step) in one pass. """
+    return self.coder.encode_many(X)
 
   def _child_evaluate(self, X1, X2):
     A = self.pack(X1)
@@ -734,22 +765,28 @@ class CartesianProductKernel(Kernel):
     inner._factor_kinds = self._factor_kinds
     return inner.to_spec(in_dim=None)
 
-  def pack(self, X):
+  def pack(self, X, many=False):
     """ The reference's list-of-lists points as the dense n x d matrix of to_spec: Euclidean, integral and
-        discrete-numeric parts become floats, the items of a Hamming part that kernel's category codes. """
+        discrete-numeric parts become floats, the items of a Hamming part that kernel's category codes.
+        many: the categories are coded a column at a time (pack_many). """
     offs, total = self.part_offsets()
     out = np.empty((len(X), total), dtype=np.float64)
     for j, (kern, off) in enumerate(zip(self.kernel_list, offs)):
       part = [pt[j] for pt in X]
       width = self._part_dim(kern)
       if _factor_kind(kern) == 'hamming':
-        block = kern.pack(part)
+        block = kern.pack_many(part) if many else kern.pack(part)
       else:
         block = np.asarray(part, dtype=np.float64).reshape((len(X), -1))
       if block.shape[1] != width:
         raise ValueError('Part %d of the points has %d columns, its kernel %d.' % (j, block.shape[1], width))
       out[:, off:off + width] = block
     return out
+
+  def pack_many(self, X):
+    """ pack() for the thousands of candidates of one acquisition step: row for row the matrix pack() gives, the
+        categories of every Hamming part coded by column instead of item by item. """
+    return self.pack(X, many=True)
 
   def _host_compose(self, X1, X2):
     """ kernel.py:525-533 with every part evaluated by its own class """

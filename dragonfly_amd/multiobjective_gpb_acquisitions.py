@@ -21,8 +21,17 @@ import numpy as np
 
 from . import gpb_acquisitions as _single
 from ._lib import MO_MAX_OBJECTIVES
-from .gpb_acquisitions import get_gp_sampler_for_parallel_strategy, maximise_acquisition
+from .gpb_acquisitions import get_gp_sampler_for_parallel_strategy
+from .gpb_acquisitions import maximise_acquisition as _maximise_acquisition
 from .kernel import _as_2d_array
+
+
+def maximise_acquisition(acq_fn, anc_data, *args, **kwargs):
+  """ gpb_acquisitions.maximise_acquisition for the closures of this module, which take rows of Euclidean points: the
+      multi-objective acquisitions of a Cartesian-product domain stay with the reference (install dispatches them). """
+  if anc_data.domain.get_type() != 'euclidean':
+    raise NotImplementedError('dragonfly_amd multi-objective acquisitions handle Euclidean domains.')
+  return _maximise_acquisition(acq_fn, anc_data, *args, **kwargs)
 
 
 def _get_ucb_beta_th(dim, time_step):

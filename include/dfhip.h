@@ -338,6 +338,25 @@ int dfh_gp_draw(dfh_gp* gp, const double* Xs, int64_t m, int64_t block,
                 double* samples_out /* [S x m] or NULL */, double* best_vals /* [S] or NULL */,
                 int64_t* best_idx /* [S] or NULL */, int32_t* jitter_powers_out /* [ceil(m/block)] or NULL */);
 
+/* Point-wise Thompson sampling: for every row i the ONE-point draw gp.draw_samples(1, [x_i]) -- with q > 0
+ * gp.draw_samples_with_hallucinated_observations(1, [x_i], Xh) -- which is what the reference's maximisers on
+ * Cartesian-product domains make of a sampler (opt/gpb_acquisitions.py:35-37 wraps it as acq_fn([x]),
+ * exd/exd_utils.py:265 calls it per candidate).  No joint draw: s_i = mu_i + sqrt(v_i) u_i with v_i the posterior
+ * variance of row i alone, unclipped; the product and the sum round separately, as L.dot(U).T + mu does
+ * (utils/general_utils.py:224-232).  A 1 x 1 stable_cholesky succeeds only for v > 0 and its ladder, which adds
+ * 10^p v, rescues neither v <= 0 nor NaN: if any row has such a variance the call returns DFH_ERR_JITTER (and the
+ * outputs are unspecified).  The posterior is the chunked one of dfh_gp_acq_argmax (the points in progress in block
+ * form, or the augmented GP where that is not positive definite -- always for fits with a projection flag), followed
+ * by one kernel per chunk for variance, sample and arg-max: no m x m or per-candidate matrix, no per-candidate launch.
+ * U: [m] standard normals; Xs, U, mean_vals and samples_out may be host or device pointers.  samples_out: optional [m];
+ * best_val / best_idx: optional, np.argmax's rule (first NaN, else first maximum).  DFH_ERR_BAD_ARG, before any
+ * launch, for m < 1, q < 0, q > 0 without Xh, and a posterior built from a Gram matrix.                             */
+int dfh_gp_ts_pointwise(dfh_gp* gp, const double* Xs, int64_t m,
+                        const double* Xh, int64_t q,            /* in-progress points, NULL / 0 = none */
+                        const double* U,                        /* [m] */
+                        double mean_const, const double* mean_vals /* [m] or NULL */,
+                        double* samples_out /* [m] or NULL */, double* best_val, int64_t* best_idx);
+
 /* add-UCB per-group posterior (gpb_acquisitions.py:139-189): for additive-kernel GPs,
  * group g's acquisition over its own candidate set Xg[m x |g|]:
  *   mu_g = scale*k_g(Xg, X[:,g]) alpha ; sd_g from the shared L ; val = mu_g + beta*sd_g.   */
