@@ -1,6 +1,7 @@
-// The GP object that lives in HBM and what its three units -- gp_fit.hip (fits, append, Gram-matrix posteriors),
-// gp_posterior.hip (chunked posterior, acquisitions) and gp_draw.hip (Thompson sampling, joint draws, multi-objective
-// calls) -- share.  Internal: include/dfhip.h is the contract.
+// The GP object that lives in HBM and what its six units share: gp_fit.hip (fits, append, Gram-matrix posteriors),
+// gp_posterior.hip (chunk sizing, the chunked posterior and its driver, the acquisition epilogues), gp_halluc.hip (points
+// in progress), gp_argmax.hip (arg-max reductions), gp_adducb.hip (the add-UCB stack) and gp_draw.hip (Thompson sampling,
+// joint draws, multi-objective calls).  Internal: include/dfhip.h is the contract.
 #pragma once
 #include "common.h"
 
@@ -69,7 +70,7 @@ inline PackedXs packed_xs_layout(const KernDev& kd, int64_t rows) {
   return PackedXs{b_xsp, b_xsp + (size_t)rows * kd.n_parts * 8};
 }
 
-// What gp_eval_driver is asked for (predict, acquisition arg-max, add-UCB of one group)
+// What gp_eval_driver is asked for (predict, acquisition arg-max, add-UCB of one group, point-wise Thompson sampling)
 struct EvalReq {
   int acq = DFH_ACQ_MEAN;
   const double* params = nullptr;                 // the acquisition's two parameters (null: zeros)
@@ -80,6 +81,8 @@ struct EvalReq {
   const double* col_w = nullptr;                  // as ChunkReq (device, [n])
   double kxx = 0.0;                               // prior variance of a stationary part range
   const double* Xh = nullptr; int64_t q = 0;      // points in progress
+  const double* U = nullptr;                      // [m] standard normals (host or device): the epilogue is the point-wise
+                                                  // Thompson draw, vals_out its samples; acq and params are not read
   double mean_const = 0.0;
   const double* mean_vals = nullptr;              // per candidate (host or device), instead of mean_const
   bool want_var = true;
@@ -87,7 +90,7 @@ struct EvalReq {
   double* best_val = nullptr; int64_t* best_idx = nullptr;                            // the winner, optional
 };
 
-// Running winner of an arg-max over chunks (numpy argmax ordering: a NaN beats everything, earlier index wins ties)
+// Running winner of an arg-max over chunks (argmax.h's ordering)
 struct Winner {
   bool have = false; double v = 0.0; int64_t i = -1;
   void merge(double ov, int64_t oi);
@@ -139,23 +142,44 @@ struct DevBlock {           // dev_alloc'ed memory of one call
   }
 };
 
+// One launch of the acquisition epilogue (posterior_acq): mean, standard deviation and value of m candidates, each where asked
+struct AcqArgs {
+  int acq = DFH_ACQ_MEAN; double p0 = 0.0, p1 = 0.0;                  // the acquisition and its two parameters
+  double kxx = 0.0; const double* kss = nullptr;                       // prior variance: one for all, or per candidate
+  double mean_const = 0.0; const double* mean_vals = nullptr;          // prior mean: one for all, or per candidate
+  const double* mu_raw = nullptr; const double* ss = nullptr; const double* ss2 = nullptr;   // (ss null: sd = 0; ss2 optional)
+  int64_t m = 0;
+  double* mu_out = nullptr; double* sd_out = nullptr; double* val_out = nullptr;
+};
+
+// Partial winners of a two-stage arg-max in SCR_RED (argmax_parts): room for cap pairs, behind them the final pair and a flag
+struct ArgmaxParts { int cap = 0; double* pv = nullptr; long* pi = nullptr; int* flag = nullptr; };
+
 // gp_posterior.hip
 bool free_plus_own_scratch(dfh_ctx* ctx, size_t* bytes);     // free device memory + the context's own scratch; false: unknown
 int64_t pick_chunk(dfh_ctx* ctx, int64_t n, int64_t m);      // candidate rows per posterior chunk
-int halluc_resolve(dfh_gp* gp, const double* Xh, int64_t q, HallucScope* s);
-int add_ucb_stacked(dfh_gp* gp, const StackedGroups& sg, const double* betas, const double* Xg_all, const int64_t* m_per_group,
-                    double* vals_out, double* best_vals, int64_t* best_idx);
-int gp_eval_driver(dfh_gp* gp, const EvalReq& rq);          // predict / acquisition arg-max / add-UCB of one group, chunk by chunk
+int gp_eval_driver(dfh_gp* gp, const EvalReq& rq);          // predict / acquisitions / point-wise TS, chunk by chunk
 // One chunk of candidates (device pointer Xs_dev, mc rows): fills mu_raw, ss (and ss2 with rq.h)
 int posterior_chunk(dfh_gp* gp, const double* Xs_dev, int64_t mc, int64_t ldxs, const ChunkReq& rq, double* mu_raw,
                     double* ss, double* ss2, ChunkOut* out = nullptr);
-__global__ void k_argmax_rows(const double* __restrict__ v, long ld, long m, double* __restrict__ out_v,
-                              long* __restrict__ out_i);
-__global__ void k_posterior_acq(int acq, double p0, double p1, double kxx, const double* __restrict__ kss,
-                                double mean_const, const double* __restrict__ mean_vals, const double* __restrict__ mu_raw,
-                                const double* __restrict__ ss, const double* __restrict__ ss2, long m,
-                                double* __restrict__ mu_out, double* __restrict__ sd_out,
-                                double* __restrict__ val_out);
+int posterior_acq(dfh_ctx* ctx, const AcqArgs& a);
+// gp_halluc.hip
+int halluc_resolve(dfh_gp* gp, const double* Xh, int64_t q, HallucScope* s);
+// posterior_chunk with the scope's points in progress; *out is what hs.cov_gp()'s call left, `spare` takes hs.aug's own mean
+int halluc_chunk(const HallucScope& hs, const double* Xs_dev, int64_t mc, int64_t ldxs, ChunkReq rq, double* mu_raw, double* ss,
+                 double* ss2, double* spare, ChunkOut* out);
+int halluc_second_row(dfh_gp* gp, const Halluc& h, const double* Xsp, const double* Nsp, const double* Kct, int64_t rows,
+                      int slot, double* ss2, double** T_out);
+// gp_argmax.hip (np.argmax's rule throughout: argmax.h)
+int argmax_parts(dfh_ctx* ctx, int cap, ArgmaxParts* p);
+// stage 2 over p's first nparts partial winners and the pair (with `flag`, p.flag too) copied back; synchronises ctx->stream
+int argmax_finish(dfh_ctx* ctx, const ArgmaxParts& p, int nparts, double* best_val, int64_t* best_idx, int* flag = nullptr);
+// per row of v [rows x ld] over its first m elements / per segment [off[g], off[g+1]) of v; indices local
+int argmax_rows(dfh_ctx* ctx, hipStream_t stream, const double* v, int64_t rows, int64_t ld, int64_t m, double* out_v, long* out_i);
+int argmax_segments(dfh_ctx* ctx, const double* v, const long* off, int G, double* out_v, long* out_i);
+// gp_adducb.hip
+int add_ucb_stacked(dfh_gp* gp, const StackedGroups& sg, const double* betas, const double* Xg_all, const int64_t* m_per_group,
+                    double* vals_out, double* best_vals, int64_t* best_idx);
 // gp_draw.hip
-__global__ void k_add_vec(double* __restrict__ y, const double* __restrict__ a, double c, long n);
+int add_vec(dfh_ctx* ctx, double* y, const double* a, double c, int64_t n);     // y[i] = (a ? a[i] : 0) + c + y[i]
 #pragma GCC visibility pop

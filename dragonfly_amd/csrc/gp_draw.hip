@@ -68,11 +68,18 @@ __global__ __launch_bounds__(256) void k_tri_draw(const double* __restrict__ L, 
   }
 }
 
-}  // namespace
-
 __global__ void k_add_vec(double* __restrict__ y, const double* __restrict__ a, double c, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) y[i] = (a ? a[i] : 0.0) + c + y[i];
+}
+
+}  // namespace
+
+// y[i] = (a ? a[i] : 0) + c + y[i]: the prior mean, per candidate or constant, onto K_tetr alpha
+int add_vec(dfh_ctx* ctx, double* y, const double* a, double c, int64_t n) {
+  hipLaunchKernelGGL(k_add_vec, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, y, a, c, (long)n);
+  DFH_LAUNCH_CHECK();
+  return DFH_OK;
 }
 
 namespace {
@@ -142,7 +149,7 @@ int64_t mo_pick_chunk(dfh_ctx* ctx, int64_t n_max, int64_t m) {
 }
 
 // The blocked-joint draw of dfh_gp_ts (include/dfhip.h) for one GP.  `gp` gives the mean; the block covariances come from
-// `cov_gp`'s factor -- gp itself, or the augmented GP of the hallucination's fall-back (HallucScope) -- and, with `h`
+// `cov_gp`'s factor -- gp itself, or the augmented GP of the hallucination's fall-back (HallucScope) -- and, with `hq` rows
 // (the block form of the q in-progress points, gp_core.py:192-220), lose the rank-q term V2^T V2 as well.
 // samples_dev (optional, device [m]) receives the draw without a trip to the host; the arg-max is skipped when neither
 // best_val nor best_idx is wanted (the multi-objective call scalarises K draws first).
@@ -152,8 +159,9 @@ int64_t mo_pick_chunk(dfh_ctx* ctx, int64_t n_max, int64_t m) {
 struct Stage1 { ChunkOut co; double* mu; };      // what the bulk-stream half left for one parity
 struct TsRun {
   // the call: filled by the caller
+  const HallucScope& hs;                         // the points in progress, resolved
   dfh_gp* gp; dfh_gp* cov_gp;
-  const Halluc* h; int64_t hq;                   // block form of the points in progress (null / 0: none)
+  int64_t hq;                                    // rows of the block form's second block row (0: none)
   const double* Xs = nullptr; int64_t m = 0, block = 0;
   const double* U = nullptr;
   double mean_const = 0.0; const double* mean_vals = nullptr;
@@ -178,8 +186,8 @@ struct TsRun {
   const double* u_c = nullptr; double* mu_raw = nullptr; double* samp = nullptr;
   int64_t blk_idx = 0;                           // blocks of the chunks before it
   Winner win; std::vector<Winner> winS;          // the single draw's winner / one per draw
-  explicit TsRun(const HallucScope& hs)
-      : gp(hs.gp), cov_gp(hs.cov_gp()), h(hs.block()), hq(hs.block_q()), ctx(hs.gp->ctx), multi(hs.gp->ctx) {}
+  explicit TsRun(const HallucScope& scope)
+      : hs(scope), gp(scope.gp), cov_gp(scope.cov_gp()), hq(scope.block_q()), ctx(scope.gp->ctx), multi(scope.gp->ctx) {}
 };
 
 // sizes, scratch, the S > 1 block, the events
@@ -240,16 +248,9 @@ int ts_stage1(TsRun& r, int64_t c) {
   st.co = ChunkOut();
   ChunkReq rq;
   rq.parity = p;
-  if (r.cov_gp != gp) {
-    // mean from the real data, V^T from the augmented factor (gp_core.py:195, 207-213); same parity buffers, in this order
-    rq.want_var = false;
-    DFH_TRY(posterior_chunk(gp, xs_c, mc, gp->d, rq, st.mu, nullptr, nullptr));
-    rq.want_var = true;
-    DFH_TRY(posterior_chunk(r.cov_gp, xs_c, mc, gp->d, rq, r.vec[p] + 2 * r.mc_max, nullptr, nullptr, &st.co));
-  } else {
-    rq.h = r.h;
-    DFH_TRY(posterior_chunk(gp, xs_c, mc, gp->d, rq, st.mu, nullptr, r.vec[p] + 2 * r.mc_max, &st.co));
-  }
+  // V^T of the factor the covariances come from; the last third of the parity's vector is ss2 or the unused mean
+  double* spare = r.vec[p] + 2 * r.mc_max;
+  DFH_TRY(halluc_chunk(r.hs, xs_c, mc, gp->d, rq, st.mu, nullptr, spare, spare, &st.co));
   DFH_HIP(hipEventRecord(r.ev_ready[p], r.bulkS));
   return DFH_OK;
 }
@@ -360,9 +361,7 @@ int ts_collect(TsRun& r) {
   const bool want_best = r.best_val || r.best_idx;
   if (S > 1) {
     if (want_best) {
-      hipLaunchKernelGGL(k_argmax_rows, dim3((unsigned)S), dim3(256), 0, mainS, (const double*)r.sampS, (long)mc, (long)mc,
-                         r.win_v, r.win_i);
-      DFH_LAUNCH_CHECK();
+      DFH_TRY(argmax_rows(ctx, mainS, r.sampS, S, mc, mc, r.win_v, r.win_i));
       DFH_HIP(hipMemcpyAsync(r.hv.data(), r.win_v, (size_t)S * 8, hipMemcpyDeviceToHost, mainS));
       DFH_HIP(hipMemcpyAsync(r.hi.data(), r.win_i, (size_t)S * 8, hipMemcpyDeviceToHost, mainS));
       DFH_HIP(hipStreamSynchronize(mainS));
@@ -409,9 +408,7 @@ int ts_run(TsRun& r) {
     r.mu_raw = r.st[r.p].mu;
     r.samp = r.vec[r.p] + r.mc_max;
     // mean_vals = test_mean + K_tetr alpha
-    hipLaunchKernelGGL(k_add_vec, dim3((unsigned)((r.mc + 255) / 256)), dim3(256), 0, ctx->stream, r.mu_raw, mv_c,
-                       mv_c ? 0.0 : r.mean_const, (long)r.mc);
-    DFH_LAUNCH_CHECK();
+    DFH_TRY(add_vec(ctx, r.mu_raw, mv_c, mv_c ? 0.0 : r.mean_const, r.mc));
     DFH_TRY(ts_factor_chunk(r));
     DFH_TRY(ts_collect(r));
     DFH_HIP(hipEventRecord(r.ev_free[r.p], r.mainS));
@@ -511,12 +508,13 @@ extern "C" int dfh_mo_ucb_argmax(dfh_gp* const* gps, int32_t k, int scal, double
       double* kss = gp->kd.stationary ? nullptr : kss_w;
       if (kss) DFH_TRY(prior_diag(ctx, gp->kd, co.Xsp, co.Nsp, mc, kss));
       SectionTimer t(ctx, DFH_T_ACQ);
-      hipLaunchKernelGGL(k_posterior_acq, dim3(grid), dim3(256), 0, ctx->stream, (int)DFH_ACQ_MEAN, 0.0, 0.0, gp->kd.kxx,
-                         (const double*)kss, mean_consts ? mean_consts[i] : 0.0,
-                         mean_vals ? mean_vals + (int64_t)i * m + i0 : (const double*)nullptr, (const double*)mu_raw,
-                         (const double*)ss, (const double*)nullptr, (long)mc, MU + (int64_t)i * mc_max,
-                         SD + (int64_t)i * mc_max, (double*)nullptr);
-      DFH_LAUNCH_CHECK();
+      AcqArgs a;                 // the mean and the standard deviation of objective i
+      a.kxx = gp->kd.kxx; a.kss = kss;
+      a.mean_const = mean_consts ? mean_consts[i] : 0.0;
+      a.mean_vals = mean_vals ? mean_vals + (int64_t)i * m + i0 : nullptr;
+      a.mu_raw = mu_raw; a.ss = ss; a.m = mc;
+      a.mu_out = MU + (int64_t)i * mc_max; a.sd_out = SD + (int64_t)i * mc_max;
+      DFH_TRY(posterior_acq(ctx, a));
     }
     SectionTimer t(ctx, DFH_T_ACQ);
     hipLaunchKernelGGL(k_mo_scalarise, dim3(grid), dim3(256), 0, ctx->stream, scal, 1, (int)k, beta, par, (const double*)MU,

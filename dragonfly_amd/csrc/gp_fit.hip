@@ -213,9 +213,7 @@ extern "C" int dfh_gp_predict_gram(dfh_gp* gp, const double* Kcross, int64_t m, 
     }
     const double* mv_c = nullptr;
     DFH_TRY(stage.mean(i0, mc, &mv_c));
-    hipLaunchKernelGGL(k_add_vec, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, ctx->stream, mu, mv_c,
-                       mv_c ? 0.0 : mean_const, (long)mc);
-    DFH_LAUNCH_CHECK();
+    DFH_TRY(add_vec(ctx, mu, mv_c, mv_c ? 0.0 : mean_const, mc));
     DFH_TRY(from_device(ctx, mu_out + i0, mu, (size_t)mc * 8));
     if (sd_out) {
       {

@@ -17,10 +17,10 @@
 //     uses a file next to the launcher's rendezvous port).
 // RCCL is loaded with dlopen on first use: single-GPU users never pay for (or depend on) it.
 #include "common.h"
+#include "argmax.h"
 #include <dlfcn.h>
 #include <stdio.h>
 #include <unistd.h>
-#include <limits.h>
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -102,14 +102,6 @@ int rccl_load(const RcclApi** out) {
     }                                                                                        \
   } while (0)
 
-bool pair_better(double va, int64_t ia, double vb, int64_t ib) {
-  const bool na = va != va, nb = vb != vb;
-  if (na || nb) { if (na && nb) return ia < ib; return na; }
-  if (va > vb) return true;
-  if (va < vb) return false;
-  return ia < ib;
-}
-
 struct Pair { double val; int64_t idx; };     // what travels: 16 bytes per rank, bit for bit
 
 // RCCL 2.27 prints a version banner on the process's stdout (C stdio) when a communicator is
@@ -149,7 +141,7 @@ extern "C" int dfh_reduce_argmax(const double* vals, const int64_t* idxs, int co
   double bv = NAN; int64_t bi = -1;
   for (int r = 0; r < count; ++r) {
     if (idxs[r] < 0) continue;                 // empty shard
-    if (bi < 0 || pair_better(vals[r], idxs[r], bv, bi)) { bv = vals[r]; bi = idxs[r]; }
+    if (bi < 0 || argmax_better(vals[r], idxs[r], bv, bi)) { bv = vals[r]; bi = idxs[r]; }
   }
   *best_val = bv; *best_idx = bi;
   return DFH_OK;
@@ -263,7 +255,7 @@ static int comm_gather_finish(dfh_comm* c, double* best_val, int64_t* best_idx) 
   double bv = NAN; int64_t bi = -1;
   for (int r = 0; r < c->nranks; ++r) {
     if (c->h_recv[r].idx < 0) continue;
-    if (bi < 0 || pair_better(c->h_recv[r].val, c->h_recv[r].idx, bv, bi)) { bv = c->h_recv[r].val; bi = c->h_recv[r].idx; }
+    if (bi < 0 || argmax_better(c->h_recv[r].val, c->h_recv[r].idx, bv, bi)) { bv = c->h_recv[r].val; bi = c->h_recv[r].idx; }
   }
   if (best_val) *best_val = bv;
   if (best_idx) *best_idx = bi;

@@ -1,5 +1,5 @@
-"""MI355X: the outputs of the GP entry points -- fit, append, posterior, acquisitions, covariance, Thompson sampling,
-joint draws, the multi-objective calls -- held bit for bit to the digests recorded in
+"""MI355X: the outputs of the GP entry points -- fit, append, posterior, acquisitions, add-UCB (the multi-fidelity one
+included), covariance, Thompson sampling (blocked and point-wise), joint draws, the multi-objective calls -- held bit for bit to the digests recorded in
 tests/golden/api_output_digests.npz (tests/api_digest_check.py), in a subprocess whose posterior chunks are the 512-row
 floor (DFH_CHUNK_GIB is read once per process), so that 1100 candidates run as three chunks."""
 import os
