@@ -107,6 +107,39 @@ _SINGLE_KINDS = {'se': KERNEL_SE, 'matern': KERNEL_MATERN, 'poly': KERNEL_POLY, 
 _PSD_FLAGS = {'guaranteed_psd': 0, 'project_first': _lib.FIT_PROJECT_FIRST, 'try_before_project': _lib.FIT_TRY_BEFORE_PROJECT}
 
 
+def _rows(Xs):
+  """ Points as the library takes them: a DeviceArray as it is, anything else as a contiguous fp64 matrix; and their number. """
+  if not isinstance(Xs, DeviceArray):
+    Xs = _f64(Xs)
+  return Xs, Xs.shape[0]
+
+
+def _halluc_rows(X_halluc):
+  """ (rows, q) of the points in progress; (None, 0) without any. """
+  return (None, 0) if X_halluc is None or len(X_halluc) == 0 else _rows(X_halluc)
+
+
+def _mean_vals_arg(mean_vals):
+  """ Per-candidate prior means as the library takes them (None: the constant alone). """
+  return mean_vals if mean_vals is None or isinstance(mean_vals, DeviceArray) else _f64(mean_vals)
+
+
+def _group_blocks(cands_per_group, sizes, betas, who):
+  """ The groups' candidates of an add-UCB call as (one flat buffer, m_g per group, beta per group): cands_per_group[g] is
+      [m_g x |group g|] -- or ONE DeviceArray holding the blocks back to back, with sizes[g] = m_g. """
+  if isinstance(cands_per_group, DeviceArray):
+    flat = cands_per_group
+    ms = np.ascontiguousarray(sizes, dtype=np.int64)
+  else:
+    blocks = [_f64(c) for c in cands_per_group]
+    ms = np.ascontiguousarray([b.shape[0] for b in blocks], dtype=np.int64)
+    flat = np.ascontiguousarray(np.concatenate([b.ravel() for b in blocks]), dtype=np.float64)
+  be = _f64(np.asarray(betas, dtype=float).reshape(-1))
+  if len(be) != len(ms):
+    raise ValueError('%s: need one beta per group.' % who)
+  return flat, ms, be
+
+
 def _psd_flags(handle_non_psd_kernels):
   """ The fit flag of one of _get_cholesky_decomp's branches (gp_core.py:827-847). """
   if handle_non_psd_kernels not in _PSD_FLAGS:
@@ -530,13 +563,10 @@ class Engine(object):
     r = None if refs is None else _f64(np.ravel(refs))
     if len(w) != k or (r is not None and len(r) != k):
       raise ValueError('Need one weight (and one reference value) per objective.')
-    Xs = Xs if isinstance(Xs, DeviceArray) else _f64(Xs)
-    m = Xs.shape[0]
-    mv = None
-    if mean_vals is not None:
-      mv = mean_vals if isinstance(mean_vals, DeviceArray) else _f64(mean_vals)
-      if tuple(mv.shape) != (k, m):
-        raise ValueError('mean_vals must have shape (objectives, candidates).')
+    Xs, m = _rows(Xs)
+    mv = _mean_vals_arg(mean_vals)
+    if mv is not None and tuple(mv.shape) != (k, m):
+      raise ValueError('mean_vals must have shape (objectives, candidates).')
     mc = _f64(np.zeros(k) if mean_consts is None else np.ravel(mean_consts))
     if len(mc) != k:
       raise ValueError('Need one mean constant per objective.')
@@ -565,7 +595,7 @@ class Engine(object):
       raise ValueError('U must hold one standard normal per objective and candidate.')
     block = int(min(block, m))
     nblk = (m + block - 1) // block
-    Xh, q = (None, 0) if X_halluc is None or len(X_halluc) == 0 else FittedGP._rows(X_halluc)
+    Xh, q = _halluc_rows(X_halluc)
     vals = np.empty(m) if return_vals else None
     jps = (C.c_int32 * (k * nblk))()
     bv, bi = C.c_double(0), C.c_int64(-1)
@@ -769,27 +799,20 @@ class FittedGP(object):
   def get_K(self):
     return self._get(GET_K, (self.n, self.n))
 
-  @staticmethod
-  def _rows(Xs):
-    if isinstance(Xs, DeviceArray):
-      return Xs, Xs.shape[0]
-    Xs = _f64(Xs)
-    return Xs, Xs.shape[0]
-
   def predict(self, Xs, want_std=True, X_halluc=None):
     """ (K(Xs,X) alpha, posterior std) -- the caller adds the mean function. """
-    Xs, m = self._rows(Xs)
+    Xs, m = _rows(Xs)
     mu = np.empty(m)
     sd = np.empty(m) if want_std else None
-    Xh, q = (None, 0) if X_halluc is None or len(X_halluc) == 0 else self._rows(X_halluc)
+    Xh, q = _halluc_rows(X_halluc)
     check(self.engine.lib.dfh_gp_predict(self.handle, _ptr(Xs), m, _ptr(Xh), q, _ptr(mu), _ptr(sd)))
     return mu, sd
 
   def predict_covar(self, Xs, X_halluc=None):
-    Xs, m = self._rows(Xs)
+    Xs, m = _rows(Xs)
     mu = np.empty(m)
     cov = np.empty((m, m))
-    Xh, q = (None, 0) if X_halluc is None or len(X_halluc) == 0 else self._rows(X_halluc)
+    Xh, q = _halluc_rows(X_halluc)
     check(self.engine.lib.dfh_gp_predict_covar(self.handle, _ptr(Xs), m, _ptr(Xh), q, _ptr(mu),
                                                _ptr(cov)))
     return mu, cov
@@ -797,12 +820,11 @@ class FittedGP(object):
   def acq_argmax(self, acq, Xs, params=(0.0, 0.0), mean_const=0.0, mean_vals=None, X_halluc=None,
                  return_vals=False):
     """ Fused posterior + acquisition + arg-max. Returns (best_val, best_idx[, vals]). """
-    Xs, m = self._rows(Xs)
+    Xs, m = _rows(Xs)
     p = (C.c_double * 2)(float(params[0]), float(params[1]) if len(params) > 1 else 0.0)
     vals = np.empty(m) if return_vals else None
-    mv = None if mean_vals is None else (mean_vals if isinstance(mean_vals, DeviceArray)
-                                         else _f64(mean_vals))
-    Xh, q = (None, 0) if X_halluc is None or len(X_halluc) == 0 else self._rows(X_halluc)
+    mv = _mean_vals_arg(mean_vals)
+    Xh, q = _halluc_rows(X_halluc)
     bv = C.c_double(0)
     bi = C.c_int64(-1)
     check(self.engine.lib.dfh_gp_acq_argmax(self.handle, ACQ_IDS[acq], p, _ptr(Xs), m, _ptr(Xh), q,
@@ -819,20 +841,19 @@ class FittedGP(object):
         gp.draw_samples_with_hallucinated_observations(num_samples, Xs, X_halluc).  U: the standard normals
         np.random.normal(size=(m, num_samples)), host array or DeviceArray.  Returns (samples [S x m] or
         None, best_vals [S], best_idx [S], jitter_powers [blocks]). """
-    Xs, m = self._rows(Xs)
+    Xs, m = _rows(Xs)
     S = int(num_samples)
     Uh = U if isinstance(U, DeviceArray) else _f64(np.ravel(U))
     if Uh.size != m * S:
       raise ValueError('U must hold one standard normal per candidate and sample.')
     block = m if block is None else int(min(block, m))
     nblk = (m + block - 1) // block
-    Xh, q = (None, 0) if X_halluc is None or len(X_halluc) == 0 else self._rows(X_halluc)
+    Xh, q = _halluc_rows(X_halluc)
     samples = np.empty((S, m)) if return_samples else None
     bvs = np.empty(max(S, 1), dtype=np.float64)
     bis = np.empty(max(S, 1), dtype=np.int64)
     jps = (C.c_int32 * nblk)()
-    mv = None if mean_vals is None else (mean_vals if isinstance(mean_vals, DeviceArray)
-                                         else _f64(mean_vals))
+    mv = _mean_vals_arg(mean_vals)
     check(self.engine.lib.dfh_gp_draw(self.handle, _ptr(Xs), m, block, _ptr(Xh), q, _ptr(Uh), S, float(mean_const),
                                       _ptr(mv), _ptr(samples), _ptr(bvs), _ptr(bis), jps))
     return samples, bvs, bis, [None if j == INT32_MIN else j for j in jps]
@@ -845,14 +866,13 @@ class FittedGP(object):
       if return_samples:
         return float(bvs[0]), int(bis[0]), samples[0], powers
       return float(bvs[0]), int(bis[0])
-    Xs, m = self._rows(Xs)
+    Xs, m = _rows(Xs)
     Uh = U if isinstance(U, DeviceArray) else _f64(np.ravel(U))
     block = int(min(block, m))
     nblk = (m + block - 1) // block
     samples = np.empty(m) if return_samples else None
     jps = (C.c_int32 * nblk)()
-    mv = None if mean_vals is None else (mean_vals if isinstance(mean_vals, DeviceArray)
-                                         else _f64(mean_vals))
+    mv = _mean_vals_arg(mean_vals)
     bv = C.c_double(0)
     bi = C.c_int64(-1)
     check(self.engine.lib.dfh_gp_ts(self.handle, _ptr(Xs), m, block, _ptr(Uh), float(mean_const),
@@ -868,14 +888,14 @@ class FittedGP(object):
         normals (host array or DeviceArray); None: Engine.random_normals(m), which continues the global np.random
         stream exactly as m calls of np.random.normal(size=(1, 1)) do.  A candidate whose variance is not positive
         raises the ValueError of an exhausted jitter ladder.  Returns (best_val, best_idx[, samples]). """
-    Xs, m = self._rows(Xs)
+    Xs, m = _rows(Xs)
     own = normals is None
     Uh = self.engine.random_normals(m) if own else (normals if isinstance(normals, DeviceArray) else _f64(np.ravel(normals)))
     if Uh.size != m:
       raise ValueError('normals must hold one standard normal per candidate.')
     samples = np.empty(m) if return_samples else None
-    mv = None if mean_vals is None else (mean_vals if isinstance(mean_vals, DeviceArray) else _f64(mean_vals))
-    Xh, q = (None, 0) if X_halluc is None or len(X_halluc) == 0 else self._rows(X_halluc)
+    mv = _mean_vals_arg(mean_vals)
+    Xh, q = _halluc_rows(X_halluc)
     bv = C.c_double(0)
     bi = C.c_int64(-1)
     try:
@@ -889,7 +909,7 @@ class FittedGP(object):
     return bv.value, bi.value
 
   def add_ucb_group(self, group, beta, Xg, return_vals=False):
-    Xg, m = self._rows(Xg)
+    Xg, m = _rows(Xg)
     vals = np.empty(m) if return_vals else None
     bv = C.c_double(0)
     bi = C.c_int64(-1)
@@ -903,17 +923,8 @@ class FittedGP(object):
     """ add-UCB for every group of the additive kernel in one device call (one posterior solve for
         all groups).  cands_per_group[g]: [m_g x |group g|] -- or ONE DeviceArray holding the groups'
         candidate blocks back to back, with sizes[g] = m_g.  Returns (best_vals, best_idx[, vals]). """
-    if isinstance(cands_per_group, DeviceArray):
-      flat = cands_per_group
-      ms = np.ascontiguousarray(sizes, dtype=np.int64)
-    else:
-      blocks = [_f64(c) for c in cands_per_group]
-      ms = np.ascontiguousarray([b.shape[0] for b in blocks], dtype=np.int64)
-      flat = np.ascontiguousarray(np.concatenate([b.ravel() for b in blocks]), dtype=np.float64)
+    flat, ms, be = _group_blocks(cands_per_group, sizes, betas, 'add_ucb_all')
     G = len(ms)
-    be = _f64(np.asarray(betas, dtype=float).reshape(-1))
-    if len(be) != G:
-      raise ValueError('add_ucb_all: need one beta per group.')
     bv = np.empty(G, dtype=np.float64)
     bi = np.empty(G, dtype=np.int64)
     vals = np.empty(int(ms.sum()), dtype=np.float64) if return_vals else None
@@ -928,7 +939,7 @@ class FittedGP(object):
         (dfh_mf_add_ucb_group; _mf_add_ucb_acq_j, opt/gpb_acquisitions.py:360-374).  `group` counts the groups of
         the domain kernel, Xg holds that group's columns. """
     z = _f64(np.ravel(z_opt))
-    Xg, m = self._rows(Xg)
+    Xg, m = _rows(Xg)
     vals = np.empty(m) if return_vals else None
     bv = C.c_double(0)
     bi = C.c_int64(-1)
@@ -943,17 +954,8 @@ class FittedGP(object):
         (dfh_mf_add_ucb_all): every group of the domain kernel in one device call, one posterior solve.
         Arguments and results as add_ucb_all. """
     z = _f64(np.ravel(z_opt))
-    if isinstance(cands_per_group, DeviceArray):
-      flat = cands_per_group
-      ms = np.ascontiguousarray(sizes, dtype=np.int64)
-    else:
-      blocks = [_f64(c) for c in cands_per_group]
-      ms = np.ascontiguousarray([b.shape[0] for b in blocks], dtype=np.int64)
-      flat = np.ascontiguousarray(np.concatenate([b.ravel() for b in blocks]), dtype=np.float64)
+    flat, ms, be = _group_blocks(cands_per_group, sizes, betas, 'mf_add_ucb_all')
     G = len(ms)
-    be = _f64(np.asarray(betas, dtype=float).reshape(-1))
-    if len(be) != G:
-      raise ValueError('mf_add_ucb_all: need one beta per group.')
     bv = np.empty(G, dtype=np.float64)
     bi = np.empty(G, dtype=np.int64)
     vals = np.empty(int(ms.sum()), dtype=np.float64) if return_vals else None

@@ -20,10 +20,17 @@ cp_acquisition_applies holds -- the device CP GP on the kernel's descriptor, ins
 step is the reference's own samples, packed in one pass, in ONE acq_argmax or (Thompson sampling: a one-point draw per
 candidate, not a joint draw) ONE thompson_pointwise call, and the tree search of an all-Euclidean product fetches its
 values a frontier per call.
+
+All three -- a Euclidean GP, BOCA's view of a multi-fidelity GP (FidelToOptGP), the device GP of a product domain -- take
+the same fused step: _fused_source decides, before any random number is drawn, which of _euclidean_step / _boca_step /
+_cp_step describes it (a _FusedStep: handle, rows, prior mean, rows in progress, index -> point), and _fused_argmax or
+_fused_thompson makes the one device call.  Add-UCB is one function (_add_ucb) over the handle's per-group and all-groups
+calls, BOCA's with the fidelity bound.  With DFH_GAP_LOG set every fused single-objective step records its margin.
 """
 import os
 from argparse import Namespace
 from copy import copy
+from functools import partial
 
 import numpy as np
 
@@ -53,18 +60,47 @@ def _candidates(anc_data, max_evals=None):
   return map_to_bounds(np.random.random((m, len(bounds))), bounds)
 
 
-def _device_candidates(gp, anc_data):
-  """ The same draw generated in HBM (Engine.random_candidates): the global np.random state is
-      continued bit for bit and left where the host draw would have left it, so the candidates
-      are the reference's -- without the host generation and the m x d copy.  Returns the
-      DeviceArray and what acq_argmax / thompson need to add the prior mean: a constant when the
-      mean function is the fitter's constant, else its values on a host copy of the candidates. """
-  bounds = np.asarray(anc_data.domain.bounds, dtype=np.float64)
-  cands = gp.device_gp.engine.random_candidates(int(anc_data.max_evals), len(bounds), bounds=bounds)
-  const = getattr(gp.mean_func, 'constant_value', None)
-  if const is not None:
-    return cands, dict(mean_const=float(const))
-  return cands, dict(mean_vals=gp.mean_func(cands.download()))
+def _draw_candidates(fitted, anc_data):
+  """ The candidates of a 'rand' step on a Euclidean domain, from the global np.random state: generated in HBM
+      (Engine.random_candidates: the state is continued bit for bit and left where the host draw would have left it, so
+      the candidates are the reference's -- without the host generation and the m x d copy), or _candidates on the host.
+      Returns (candidates, index -> host point). """
+  if DEVICE_CANDIDATES:
+    bounds = np.asarray(anc_data.domain.bounds, dtype=np.float64)
+    cands = fitted.engine.random_candidates(int(anc_data.max_evals), len(bounds), bounds=bounds)
+    return cands, cands.row
+  cands = _candidates(anc_data)
+  return cands, cands.__getitem__
+
+
+def _host_rows(cands):
+  return cands if isinstance(cands, np.ndarray) else cands.download()
+
+
+def _mean_constant(mean_func):
+  """ The value of the fitter's constant mean (gp_core.ConstantMean), or None for any other mean function. """
+  const = getattr(mean_func, 'constant_value', None)
+  return None if const is None else float(const)
+
+
+def _prior_mean(mean_func, points):
+  """ What a fused call adds to K(x, X) alpha, as its keyword arguments: the constant of a constant mean, else the mean
+      function's values on points() -- the host form of the candidates, fetched only when it is needed. """
+  const = _mean_constant(mean_func)
+  return dict(mean_vals=mean_func(points())) if const is None else dict(mean_const=const)
+
+
+def _normals_in_hbm(fitted):
+  return DEVICE_CANDIDATES and getattr(getattr(fitted, 'engine', None), 'random_normals', None) is not None
+
+
+def _standard_normals(fitted, m, draws=1):
+  """ np.random.normal(size=(m, 1)) of draw_gaussian_samples (general_utils.py:230), `draws` times in a row, as one
+      stream -- generated in HBM where the candidates are (Engine.random_normals continues the global state bit for bit,
+      the cached second gaussian included; free() the DeviceArray after the call), else drawn here. """
+  if _normals_in_hbm(fitted):
+    return fitted.engine.random_normals(draws * m)
+  return np.concatenate([np.random.normal(size=(m, 1)).ravel() for _ in range(draws)])
 
 
 def _is_rand_euclidean(anc_data):
@@ -80,21 +116,10 @@ def _is_device_gp(gp):
   return isinstance(gp, GP) and gp.num_tr_data > 0 and not gp._generic    # pylint: disable=protected-access
 
 
-def _can_fuse(gp, anc_data):
-  """ The fused candidates -> posterior -> acquisition -> arg-max call needs a device kernel; GPs
-      whose kernel the host evaluates take the reference's closure route (batched gp.eval).  In a
-      multi-fidelity run only BOCA's own view of a device GP (FidelToOptGP) is fused. """
-  if not _is_rand_euclidean(anc_data):
-    return False
-  if isinstance(gp, FidelToOptGP):
-    return gp.is_fusable()
-  return _is_device_gp(gp) and not getattr(anc_data, 'is_mf', False)
-
-
 class FidelToOptGP(object):
   """ The GP BOCA hands the acquisitions: the multi-fidelity GP seen at fidel_to_opt
       (_get_fidel_to_opt_gp, gpb_acquisitions.py:314-332) -- the reference Namespace's five attributes,
-      plus the GP and the fidelity themselves, so that the acquisitions can take the fused route: the
+      plus the GP and the fidelity themselves, so that the acquisitions can take the fused route (_boca_step): the
       candidates drawn as ever, joined with the fidelity in HBM (Engine.join_fixed) and handed to the
       joint GP's fused calls with the joint (fidelity, point) pairs in progress. """
 
@@ -121,42 +146,6 @@ class FidelToOptGP(object):
     """ A Euclidean multi-fidelity mirror GP with a device kernel: its joint points are [z, x] rows. """
     from .mf_gp import EuclideanMFGP
     return isinstance(self.mfgp, EuclideanMFGP) and _is_device_gp(self.mfgp)
-
-  def fused_inputs(self, anc_data):
-    """ (candidates, joint candidates in HBM, prior-mean arguments, joint pairs in progress) of a fused call: the
-        candidates come from the global np.random state exactly as for a single-fidelity GP. """
-    engine = self.mfgp.device_gp.engine
-    if DEVICE_CANDIDATES:
-      bounds = np.asarray(anc_data.domain.bounds, dtype=np.float64)
-      cands = engine.random_candidates(int(anc_data.max_evals), len(bounds), bounds=bounds)
-    else:
-      cands = _candidates(anc_data)
-    joint = engine.join_fixed(self.fidel_to_opt, cands)
-    const = getattr(self.mfgp.mean_func, 'constant_value', None)
-    if const is not None:
-      mean = dict(mean_const=float(const))
-    else:
-      host = cands if isinstance(cands, np.ndarray) else cands.download()
-      mean = dict(mean_vals=self.mfgp.mean_func(self._joint(list(host))))
-    pts = _in_progress(anc_data)
-    return cands, joint, mean, (None if pts is None else _as_2d_array(pts))
-
-
-def _winning_row(cands, idx):
-  return cands[idx] if isinstance(cands, np.ndarray) else cands.row(idx)
-
-
-def _fused_argmax_at_fidel(view, acq, params, anc_data):
-  """ _fused_argmax for BOCA's view: the joint GP's fused call on [fidel_to_opt, candidate] rows; the
-      winner is read from the un-joined candidates. """
-  cands, joint, mean, Xh = view.fused_inputs(anc_data)
-  if gaplog.ENABLED:
-    _, idx, vals = view.mfgp.device_gp.acq_argmax(acq, joint, params=params, X_halluc=Xh, return_vals=True, **mean)
-    gaplog.top2('acq_argmax', vals)
-  else:
-    _, idx = view.mfgp.device_gp.acq_argmax(acq, joint, params=params, X_halluc=Xh, **mean)
-  return _winning_row(cands, idx)
-
 
 def _fortran_direct_available():
   """ True when a Dragonfly with its compiled DIRECT is importable (oper_utils.py:21-25). """
@@ -290,51 +279,6 @@ def cp_acquisition_applies(acq, gp, anc_data):
   return acq == 'ts' or _cp_maximiser(anc_data) is not None
 
 
-def _is_cp_rand(gp, anc_data):
-  """ A step the fused calls take on packed Cartesian-product candidates. """
-  return _is_cp_device_step(gp, anc_data) and _cp_maximiser(anc_data) == 'rand'
-
-
-def _cp_fused_inputs(gp, anc_data):
-  """ (candidates, the same packed into the descriptor's dense layout in one pass, prior-mean arguments, packed points
-      in progress or None) of a fused call on a Cartesian-product domain. """
-  cands = _cp_candidates(anc_data)
-  packed = gp.kernel.pack_many(cands)
-  const = getattr(gp.mean_func, 'constant_value', None)
-  mean = dict(mean_const=float(const)) if const is not None else dict(mean_vals=gp.mean_func(cands))
-  pts = _in_progress(anc_data)
-  return cands, packed, mean, (None if pts is None else gp.kernel.pack_many(pts))
-
-
-def _cp_fused_argmax(gp, acq, params, anc_data):
-  """ _fused_argmax on a Cartesian-product domain: the reference's samples, packed, in ONE acq_argmax; the point
-      returned is the winning sample object itself. """
-  cands, packed, mean, Xh = _cp_fused_inputs(gp, anc_data)
-  if gaplog.ENABLED:
-    _, idx, vals = gp.device_gp.acq_argmax(acq, packed, params=params, X_halluc=Xh, return_vals=True, **mean)
-    gaplog.top2('acq_argmax', vals)
-  else:
-    _, idx = gp.device_gp.acq_argmax(acq, packed, params=params, X_halluc=Xh, **mean)
-  return cands[idx]
-
-
-def _cp_thompson(gp, anc_data):
-  """ asy_ts on a Cartesian-product domain.  The reference draws the samples of the domain, then calls the sampler on
-      one point at a time: per candidate a one-point posterior, its 1 x 1 stable_cholesky and one
-      np.random.normal(size=(1, 1)) -- no joint draw.  Here: the same samples, then the m normals in the same order
-      (generated in HBM where the engine can, the global state left where m such calls leave it), and ONE
-      thompson_pointwise. """
-  cands, packed, mean, Xh = _cp_fused_inputs(gp, anc_data)
-  on_device = DEVICE_CANDIDATES and getattr(gp.device_gp.engine, 'random_normals', None) is not None
-  normals = None if on_device else np.random.normal(size=(len(cands), 1)).ravel()
-  if gaplog.ENABLED:
-    _, idx, samples = gp.device_gp.thompson_pointwise(packed, normals, X_halluc=Xh, return_samples=True, **mean)
-    gaplog.top2('thompson', samples)
-  else:
-    _, idx = gp.device_gp.thompson_pointwise(packed, normals, X_halluc=Xh, **mean)
-  return cands[idx]
-
-
 class _BoxDomain(object):
   """ The Euclidean sub-domain of one additive group (EuclideanDomain(domain_bounds[group_j]),
       gpb_acquisitions.py:180). """
@@ -392,26 +336,98 @@ def get_gp_sampler_for_parallel_strategy(gp, anc_data):
   return lambda x: gp.draw_samples(1, x).ravel()
 
 
-def _fused_argmax(gp, acq, params, anc_data):
-  """ Candidates -> posterior -> acquisition -> arg-max on the device; returns the point. """
+# The fused step ---------------------------------------------------------------------------------
+class _FusedStep(object):
+  """ One fused device call of a 'rand' step, described: the fitted handle; the candidates as rows the kernel reads; the
+      prior-mean keyword arguments; the rows in progress, or None; index -> the point the step returns.  pointwise: Thompson
+      sampling draws one point at a time, as the reference does on a Cartesian-product domain, not jointly. """
+
+  def __init__(self, fitted, rows, mean, in_progress, point, pointwise=False):
+    self.fitted, self.rows, self.mean, self.in_progress, self.point = fitted, rows, mean, in_progress, point
+    self.pointwise = pointwise
+
+
+def _euclidean_step(gp, anc_data):
+  """ A Euclidean device GP: the rows are the candidates. """
+  cands, point = _draw_candidates(gp.device_gp, anc_data)
+  if isinstance(cands, np.ndarray):
+    # host candidates have always gone with the mean function's values, constant or not
+    mean = dict(mean_vals=gp.mean_func(cands))
+  else:
+    mean = _prior_mean(gp.mean_func, cands.download)
+  return _FusedStep(gp.device_gp, cands, mean, _halluc_points(anc_data), point)
+
+
+def _boca_step(view, anc_data):
+  """ BOCA's view: the same candidates, joined in HBM with fidel_to_opt into rows of the joint GP; the prior mean is
+      the joint GP's on the joint points, the points in progress are the joint pairs; the point is the un-joined
+      candidate. """
+  fitted = view.mfgp.device_gp
+  cands, point = _draw_candidates(fitted, anc_data)
+  joint = fitted.engine.join_fixed(view.fidel_to_opt, cands)
+  mean = _prior_mean(view.mfgp.mean_func, lambda: view._joint(list(_host_rows(cands))))      # pylint: disable=protected-access
+  pts = _in_progress(anc_data)
+  return _FusedStep(fitted, joint, mean, None if pts is None else _as_2d_array(pts), point)
+
+
+def _cp_step(gp, anc_data):
+  """ The device GP of a Cartesian-product domain: the reference's samples, packed into the descriptor's dense layout in
+      one pass, as are the points in progress; the point is the winning sample object itself. """
+  cands = _cp_candidates(anc_data)
+  pts = _in_progress(anc_data)
+  return _FusedStep(gp.device_gp, gp.kernel.pack_many(cands), _prior_mean(gp.mean_func, lambda: cands),
+                    None if pts is None else gp.kernel.pack_many(pts), cands.__getitem__, pointwise=True)
+
+
+def _fused_source(gp, anc_data, thompson=False):
+  """ Which of the three builds this step's _FusedStep, or None for the reference's closure route; decided before any
+      random number is drawn.  The fused call needs a device kernel and the 'rand' maximiser.  In a multi-fidelity run
+      only BOCA's own view of a device GP is fused -- though Thompson sampling (thompson=True) has never asked a plain
+      Euclidean GP whether the run is multi-fidelity.  Thompson sampling also needs a handle that draws the way the step
+      asks: with the points in progress in one call (FittedGP.fused_draws), or point-wise on a product domain. """
   if isinstance(gp, FidelToOptGP):
-    return _fused_argmax_at_fidel(gp, acq, params, anc_data)
-  Xh = _halluc_points(anc_data)
-  if DEVICE_CANDIDATES:
-    cands, mean = _device_candidates(gp, anc_data)
-    if gaplog.ENABLED:
-      _, idx, vals = gp.device_gp.acq_argmax(acq, cands, params=params, X_halluc=Xh, return_vals=True, **mean)
-      gaplog.top2('acq_argmax', vals)
-      return cands.row(idx)
-    _, idx = gp.device_gp.acq_argmax(acq, cands, params=params, X_halluc=Xh, **mean)
-    return cands.row(idx)
-  cands = _candidates(anc_data)
+    if not (_is_rand_euclidean(anc_data) and gp.is_fusable()):
+      return None
+    source, fitted, waiting = _boca_step, gp.mfgp.device_gp, _in_progress(anc_data)
+  elif _is_rand_euclidean(anc_data) and _is_device_gp(gp) and (thompson or not getattr(anc_data, 'is_mf', False)):
+    source, fitted, waiting = _euclidean_step, gp.device_gp, _halluc_points(anc_data)
+  elif _is_cp_device_step(gp, anc_data) and _cp_maximiser(anc_data) == 'rand':
+    return _cp_step if not thompson or hasattr(gp.device_gp, 'thompson_pointwise') else None
+  else:
+    return None
+  if thompson and waiting is not None and not getattr(fitted, 'fused_draws', False):
+    return None
+  return source
+
+
+def _fused_argmax(step, acq, params):
+  """ Posterior -> acquisition -> arg-max (first NaN, else first maximum) on the device; returns the point. """
+  extra = dict(return_vals=True) if gaplog.ENABLED else {}
+  out = step.fitted.acq_argmax(acq, step.rows, params=params, X_halluc=step.in_progress, **step.mean, **extra)
   if gaplog.ENABLED:
-    _, idx, vals = gp.device_gp.acq_argmax(acq, cands, params=params, mean_vals=gp.mean_func(cands), X_halluc=Xh, return_vals=True)
-    gaplog.top2('acq_argmax', vals)
-    return cands[idx]
-  _, idx = gp.device_gp.acq_argmax(acq, cands, params=params, mean_vals=gp.mean_func(cands), X_halluc=Xh)
-  return cands[idx]
+    gaplog.top2('acq_argmax', out[2])
+  return step.point(out[1])
+
+
+def _fused_thompson(step):
+  """ Thompson sampling on the device.  Jointly: one draw over all m rows -- covariance, stable_cholesky, L u and the
+      arg-max stay there, and with the normals generated in HBM nothing of size m crosses PCIe in either direction.
+      Point-wise: per row a one-point posterior, its 1 x 1 stable_cholesky and one normal, the m normals in the order of m
+      calls of np.random.normal(size=(1, 1)), in ONE thompson_pointwise -- which generates them itself when handed None. """
+  m = step.rows.shape[0]
+  extra = dict(return_samples=True) if gaplog.ENABLED else {}
+  normals = None if step.pointwise and _normals_in_hbm(step.fitted) else _standard_normals(step.fitted, m)
+  if step.pointwise:
+    out = step.fitted.thompson_pointwise(step.rows, normals, X_halluc=step.in_progress, **step.mean, **extra)
+  else:
+    if step.in_progress is not None:      # (a handle without fused_draws takes no such argument)
+      extra['X_halluc'] = step.in_progress
+    out = step.fitted.thompson(step.rows, normals, block=m, **step.mean, **extra)
+  if hasattr(normals, 'free'):
+    normals.free()
+  if gaplog.ENABLED:
+    gaplog.top2('thompson', out[2])
+  return step.point(out[1])
 
 
 def _get_syn_recommendations_from_asy(asy_acq, num_workers, list_of_gps, anc_datas):
@@ -440,10 +456,9 @@ def _host_acquisition(gp, anc_data, formula):
 
 def _acquire(gp, anc_data, acq, params, formula):
   """ One acquisition step: fused on the device when possible, the closure route otherwise. """
-  if _can_fuse(gp, anc_data):
-    return _fused_argmax(gp, acq, params, anc_data)
-  if _is_cp_rand(gp, anc_data):
-    return _cp_fused_argmax(gp, acq, params, anc_data)
+  source = _fused_source(gp, anc_data)
+  if source is not None:
+    return _fused_argmax(source(gp, anc_data), acq, params)
   return _host_acquisition(gp, anc_data, formula)
 
 
@@ -466,61 +481,10 @@ def asy_ts(gp, anc_data):
   if anc_data.acq_opt_method != 'rand':
     anc_data.max_evals *= 4
     anc_data.acq_opt_method = 'rand'
-  if isinstance(gp, FidelToOptGP) and _can_fuse(gp, anc_data):
-    return _ts_at_fidel(gp, anc_data)
-  if _is_cp_rand(gp, anc_data) and hasattr(gp.device_gp, 'thompson_pointwise'):
-    return _cp_thompson(gp, anc_data)
-  Xh = _halluc_points(anc_data)
-  fused = anc_data.domain.get_type() == 'euclidean' and _is_device_gp(gp)
-  if fused and Xh is not None:
-    # with evaluations in progress: only where the fitted handle draws with them in one call (FittedGP.fused_draws)
-    fused = getattr(gp.device_gp, 'fused_draws', False)
-  if not fused:
-    return maximise_acquisition(get_gp_sampler_for_parallel_strategy(gp, anc_data), anc_data,
-                                vectorised=True)
-  halluc = {} if Xh is None else {'X_halluc': Xh}
-  # covariance, stable_cholesky, L u and the arg-max stay on the device; the standard normals are
-  # np.random.normal(size=(m, 1)) as in draw_gaussian_samples (general_utils.py:230) -- drawn in HBM
-  # as well (Engine.random_normals continues the global state bit for bit): nothing of size m
-  # crosses PCIe in either direction
-  if DEVICE_CANDIDATES:
-    cands, mean = _device_candidates(gp, anc_data)
-    normals = gp.device_gp.engine.random_normals(cands.shape[0])
-    _, idx = gp.device_gp.thompson(cands, normals, block=cands.shape[0], **mean, **halluc)
-    normals.free()
-    return cands.row(idx)
-  cands = _candidates(anc_data)
-  normals = np.random.normal(size=(len(cands), 1)).ravel()
-  if gaplog.ENABLED:
-    _, idx, samples, _ = gp.device_gp.thompson(cands, normals, block=len(cands), mean_vals=gp.mean_func(cands), return_samples=True, **halluc)
-    gaplog.top2('thompson', samples)
-    return cands[idx]
-  _, idx = gp.device_gp.thompson(cands, normals, block=len(cands), mean_vals=gp.mean_func(cands), **halluc)
-  return cands[idx]
-
-
-def _ts_at_fidel(view, anc_data):
-  """ asy_ts for BOCA's view: one joint draw over the [fidel_to_opt, candidate] rows on the device,
-      the joint pairs in progress hallucinated where the fitted handle can (FittedGP.fused_draws). """
-  pts = _in_progress(anc_data)
-  if pts is not None and not getattr(view.mfgp.device_gp, 'fused_draws', False):
-    return maximise_acquisition(get_gp_sampler_for_parallel_strategy(view, anc_data), anc_data, vectorised=True)
-  cands, joint, mean, Xh = view.fused_inputs(anc_data)
-  halluc = {} if Xh is None else {'X_halluc': Xh}
-  device_gp = view.mfgp.device_gp
-  m = joint.shape[0]
-  if DEVICE_CANDIDATES:
-    normals = device_gp.engine.random_normals(m)
-  else:
-    normals = np.random.normal(size=(m, 1)).ravel()
-  if gaplog.ENABLED:
-    _, idx, samples, _ = device_gp.thompson(joint, normals, block=m, return_samples=True, **mean, **halluc)
-    gaplog.top2('thompson', samples)
-  else:
-    _, idx = device_gp.thompson(joint, normals, block=m, **mean, **halluc)
-  if DEVICE_CANDIDATES:
-    normals.free()
-  return _winning_row(cands, idx)
+  source = _fused_source(gp, anc_data, thompson=True)
+  if source is None:
+    return maximise_acquisition(get_gp_sampler_for_parallel_strategy(gp, anc_data), anc_data, vectorised=True)
+  return _fused_thompson(source(gp, anc_data))
 
 
 # Add-UCB -------------------------------------------------------------------------------------
@@ -529,18 +493,17 @@ def _get_add_ucb_beta_th(dim, time_step):
   return np.sqrt(0.2 * dim * np.log(2 * dim * time_step + 1))
 
 
-def _add_ucb(gp, add_kernel, mean_funcs, anc_data):
-  """ gpb_acquisitions.py:139-189: one UCB maximisation per additive group, each over its own
+def _add_ucb(fitted, group_ucb, all_ucb, groupings, mean_funcs, anc_data):
+  """ gpb_acquisitions.py:139-189, and :334-388 for BOCA: one UCB maximisation per additive group, each over its own
       candidate set (max_evals // number of groups points, drawn group by group from the global
       np.random state as the reference's loop draws them; the acquisition itself consumes no random
-      numbers), the winners assembled coordinate-wise.  With 'rand' all groups go to the device in
+      numbers), the winners assembled coordinate-wise.  group_ucb and all_ucb are the fitted handle's calls for one group
+      and for all of them (add_ucb_group / add_ucb_all; for a multi-fidelity GP with an additive domain model
+      mf_add_ucb_group / mf_add_ucb_all with fidel_to_opt bound).  With 'rand' all groups go to the device in
       ONE call: the per-group posteriors share the factor L and alpha in HBM and one triangular
       solve.  Other maximisers, and per-group mean functions, take the reference's loop. """
-  if not isinstance(add_kernel, AdditiveKernel):
-    raise TypeError('add_ucb needs a GP with an AdditiveKernel.')
-  groupings = add_kernel.groupings
   all_bounds = np.asarray(anc_data.domain_bounds, dtype=np.float64)
-  per_group_evals = int(anc_data.max_evals // len(add_kernel.kernel_list))
+  per_group_evals = int(anc_data.max_evals // len(groupings))
   betas = [_get_add_ucb_beta_th(len(grp), anc_data.t) for grp in groupings]
   point = np.zeros((sum(len(grp) for grp in groupings),))
   if mean_funcs is not None or not _is_rand_euclidean(anc_data):
@@ -554,33 +517,36 @@ def _add_ucb(gp, add_kernel, mean_funcs, anc_data):
     for j, (grp, beta, mean_func_j) in enumerate(zip(groupings, betas, mean_funcs)):
       def _group_acq(X_j, _j=j, _beta=beta, _mean=mean_func_j):
         X_j = _as_2d_array(X_j)
-        return gp.device_gp.add_ucb_group(_j, _beta, X_j, return_vals=True)[2] + _mean(X_j)
+        return group_ucb(_j, _beta, X_j, return_vals=True)[2] + _mean(X_j)
       anc_j = copy(anc_data)
       anc_j.max_evals = per_group_evals
       anc_j.domain = _BoxDomain(all_bounds[grp])
       point[grp] = maximise_acquisition(_group_acq, anc_j)
     return point
   if DEVICE_CANDIDATES:
-    engine = gp.device_gp.engine
+    engine = fitted.engine
     widths = [len(grp) for grp in groupings]
     starts = np.concatenate([[0], np.cumsum([per_group_evals * w for w in widths])])
     flat = engine.empty((int(starts[-1]),))
     for grp, start in zip(groupings, starts):
       engine.random_candidates(per_group_evals, len(grp), bounds=all_bounds[grp], out=flat.offset(start))
-    _, winners = gp.device_gp.add_ucb_all(betas, flat, sizes=[per_group_evals] * len(groupings))
+    _, winners = all_ucb(betas, flat, sizes=[per_group_evals] * len(groupings))
     for grp, start, idx in zip(groupings, starts, winners):
       point[grp] = flat.slice(int(start) + int(idx) * len(grp), len(grp))
     return point
   cands = [map_to_bounds(np.random.random((per_group_evals, len(grp))), all_bounds[grp])
            for grp in groupings]
-  _, winners = gp.device_gp.add_ucb_all(betas, cands)
+  _, winners = all_ucb(betas, cands)
   for grp, cands_g, idx in zip(groupings, cands, winners):
     point[grp] = cands_g[int(idx)]
   return point
 
 
 def asy_add_ucb(gp, anc_data):
-  return _add_ucb(gp, gp.kernel, None, anc_data)
+  if not isinstance(gp.kernel, AdditiveKernel):
+    raise TypeError('add_ucb needs a GP with an AdditiveKernel.')
+  fitted = gp.device_gp
+  return _add_ucb(fitted, fitted.add_ucb_group, fitted.add_ucb_all, gp.kernel.groupings, None, anc_data)
 
 
 # UCB ------------------------------------------------------------------------------------------
@@ -624,10 +590,9 @@ def _ttei(gp_eval, anc_data, ref_point, gp=None):
   """ Expected improvement over a reference point, with the combined standard deviation
       (gpb_acquisitions.py:269-280). """
   ref_mean, ref_std = [float(np.ravel(v)[0]) for v in gp_eval([ref_point])]
-  if gp is not None and _can_fuse(gp, anc_data):
-    return _fused_argmax(gp, 'ttei', (ref_mean, ref_std), anc_data)
-  if gp is not None and _is_cp_rand(gp, anc_data):
-    return _cp_fused_argmax(gp, 'ttei', (ref_mean, ref_std), anc_data)
+  source = None if gp is None else _fused_source(gp, anc_data)
+  if source is not None:
+    return _fused_argmax(source(gp, anc_data), 'ttei', (ref_mean, ref_std))
   def _tt_ei_acq(x):
     mu, sigma = gp_eval(x)
     comb_std = np.sqrt(ref_std ** 2 + sigma ** 2)
@@ -663,54 +628,14 @@ def _get_fidel_to_opt_gp(mfgp, fidel_to_opt):
   return FidelToOptGP(mfgp, fidel_to_opt)
 
 
-def _add_ucb_for_boca(mfgp, fidel_to_opt, mean_funcs, anc_data):
-  """ gpb_acquisitions.py:334-388: _add_ucb for a multi-fidelity GP with an additive domain model, at
-      fidel_to_opt.  Group j's cross matrix is kern_scale * k_fid(Z, fidel_to_opt) * k_j(x_j, X[:, group j]),
-      its prior variance kern_scale * k_fid(f2o, f2o) * k_j(x, x); L and alpha are the joint GP's and stay
-      in HBM (FittedGP.mf_add_ucb_group / _all).  The candidates are drawn as _add_ucb draws them. """
-  domain_kernel = mfgp.domain_kernel
-  groupings = domain_kernel.groupings
-  num_groups = len(domain_kernel.kernel_list)
-  all_bounds = np.asarray(anc_data.domain_bounds, dtype=np.float64)
-  per_group_evals = int(anc_data.max_evals // num_groups)
-  betas = [_get_add_ucb_beta_th(len(grp), anc_data.t) for grp in groupings]
-  point = np.zeros((sum(len(grp) for grp in groupings),))
-  device_gp = mfgp.device_gp
-  if mean_funcs is not None or not _is_rand_euclidean(anc_data):
-    if mean_funcs is None:
-      mean_funcs = lambda x: np.array([0] * len(x))
-    if not hasattr(mean_funcs, '__iter__'):
-      mean_funcs = [mean_funcs] * num_groups
-    for j, (grp, beta, mean_func_j) in enumerate(zip(groupings, betas, mean_funcs)):
-      def _mf_group_acq(X_j, _j=j, _beta=beta, _mean=mean_func_j):
-        X_j = _as_2d_array(X_j)
-        return device_gp.mf_add_ucb_group(fidel_to_opt, _j, _beta, X_j, return_vals=True)[2] + _mean(X_j)
-      anc_j = copy(anc_data)
-      anc_j.max_evals = per_group_evals
-      anc_j.domain = _BoxDomain(all_bounds[grp])
-      point[grp] = maximise_acquisition(_mf_group_acq, anc_j)
-    return point
-  if DEVICE_CANDIDATES:
-    engine = device_gp.engine
-    widths = [len(grp) for grp in groupings]
-    starts = np.concatenate([[0], np.cumsum([per_group_evals * w for w in widths])])
-    flat = engine.empty((int(starts[-1]),))
-    for grp, start in zip(groupings, starts):
-      engine.random_candidates(per_group_evals, len(grp), bounds=all_bounds[grp], out=flat.offset(start))
-    _, winners = device_gp.mf_add_ucb_all(fidel_to_opt, betas, flat, sizes=[per_group_evals] * num_groups)
-    for grp, start, idx in zip(groupings, starts, winners):
-      point[grp] = flat.slice(int(start) + int(idx) * len(grp), len(grp))
-    return point
-  cands = [map_to_bounds(np.random.random((per_group_evals, len(grp))), all_bounds[grp]) for grp in groupings]
-  _, winners = device_gp.mf_add_ucb_all(fidel_to_opt, betas, cands)
-  for grp, cands_g, idx in zip(groupings, cands, winners):
-    point[grp] = cands_g[int(idx)]
-  return point
-
-
 def asy_add_ucb_for_boca(mfgp, fidel_to_opt, anc_data):
-  """ gpb_acquisitions.py:390-392 """
-  return _add_ucb_for_boca(mfgp, fidel_to_opt, None, anc_data)
+  """ gpb_acquisitions.py:334-392: _add_ucb for a multi-fidelity GP with an additive domain model, at fidel_to_opt.
+      Group j's cross matrix is kern_scale * k_fid(Z, fidel_to_opt) * k_j(x_j, X[:, group j]), its prior variance
+      kern_scale * k_fid(f2o, f2o) * k_j(x, x); L and alpha are the joint GP's and stay in HBM
+      (FittedGP.mf_add_ucb_group / _all). """
+  fitted = mfgp.device_gp
+  return _add_ucb(fitted, partial(fitted.mf_add_ucb_group, fidel_to_opt), partial(fitted.mf_add_ucb_all, fidel_to_opt),
+                  mfgp.domain_kernel.groupings, None, anc_data)
 
 
 def syn_add_ucb_for_boca(num_workers, list_of_mfgps, fidel_to_opt, anc_data):

@@ -22,6 +22,7 @@ import numpy as np
 from . import gpb_acquisitions as _single
 from ._lib import MO_MAX_OBJECTIVES
 from .gpb_acquisitions import get_gp_sampler_for_parallel_strategy
+from .gpb_acquisitions import _draw_candidates, _host_rows, _mean_constant, _standard_normals      # pylint: disable=protected-access
 from .gpb_acquisitions import maximise_acquisition as _maximise_acquisition
 from .kernel import _as_2d_array
 
@@ -58,24 +59,13 @@ def _device_gps(gps, anc_data):
 
 
 def _prior_means(gps, cands):
-  """ What the device call adds to K(x, X) alpha per objective: the fitters' constant means, or the mean
-      functions' values on the candidates (a host copy of them when they were generated in HBM). """
-  consts = [getattr(gp.mean_func, 'constant_value', None) for gp in gps]
-  if all(c is not None for c in consts):
-    return dict(mean_consts=[float(c) for c in consts])
-  host = cands if isinstance(cands, np.ndarray) else cands.download()
+  """ What the device call adds to K(x, X) alpha per objective, by the single-objective rule: the fitters' constant
+      means, or the mean functions' values on the candidates (a host copy of them when they were generated in HBM). """
+  consts = [_mean_constant(gp.mean_func) for gp in gps]
+  if None not in consts:
+    return dict(mean_consts=consts)
+  host = _host_rows(cands)
   return dict(mean_vals=np.array([np.asarray(gp.mean_func(host), dtype=np.float64).ravel() for gp in gps]))
-
-
-def _rand_candidates(fitted, anc_data):
-  """ random_maximise's draw (utils/oper_utils.py:61-62) from the global np.random state: in HBM, or
-      on the host with DFH_HOST_CANDIDATES=1.  Returns (candidates, row(i) -> host point). """
-  if _single.DEVICE_CANDIDATES:
-    bounds = np.asarray(anc_data.domain.bounds, dtype=np.float64)
-    cands = fitted[0].engine.random_candidates(int(anc_data.max_evals), len(bounds), bounds=bounds)
-    return cands, cands.row
-  cands = _single._candidates(anc_data)       # pylint: disable=protected-access
-  return cands, lambda idx: cands[idx]
 
 
 def _scal_args(scal, anc_data):
@@ -113,14 +103,10 @@ def _mo_ts(scal, gps, anc_data):
     return maximise_acquisition(_host_ts_acquisition(scal, gps, anc_data), anc_data, vectorised=True)
   engine = fitted[0].engine
   Xh = _single._halluc_points(anc_data)       # pylint: disable=protected-access
-  cands, row = _rand_candidates(fitted, anc_data)
+  cands, row = _draw_candidates(fitted[0], anc_data)
   m, k = cands.shape[0], len(fitted)
-  # np.random.normal(size=(m, 1)) of draw_gaussian_samples (utils/general_utils.py:230), once per objective in
-  # the order the reference's loop asks: one stream of k m normals (the cached second gaussian carries over)
-  if _single.DEVICE_CANDIDATES:
-    normals = engine.random_normals(k * m)
-  else:
-    normals = np.concatenate([np.random.normal(size=(m, 1)).ravel() for _ in range(k)])
+  # once per objective in the order the reference's loop asks: one stream of k m normals
+  normals = _standard_normals(fitted[0], m, draws=k)
   _, idx = engine.mo_thompson(fitted, *_scal_args(scal, anc_data), Xs=cands, U=normals, block=m, X_halluc=Xh,
                               **_prior_means(gps, cands))
   if hasattr(normals, 'free'):
@@ -170,7 +156,7 @@ def _mo_ucb(scal, gps, anc_data):
   engine = fitted[0].engine
   scal_args = _scal_args(scal, anc_data)
   if str(anc_data.acq_opt_method).lower().startswith('rand'):
-    cands, row = _rand_candidates(fitted, anc_data)
+    cands, row = _draw_candidates(fitted[0], anc_data)
     _, idx = engine.mo_ucb_argmax(fitted, scal_args[0], beta_th, scal_args[1], scal_args[2], cands,
                                   **_prior_means(gps, cands))
     return row(idx)
