@@ -120,6 +120,9 @@ SIGNATURES = {
   'dfh_mo_ts_argmax': (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, c_double_p, c_int64_p, C.c_void_p]),
+  'dfh_mo_ts_pointwise': (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, c_double_p, c_int64_p]),
   # multi-GPU: host-only contract, one-process-per-GPU communicator, in-process fan-out
   'dfh_shard_bounds': (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int64, c_int64_p, c_int64_p]),
   'dfh_reduce_argmax': (C.c_int, [c_double_p, c_int64_p, C.c_int, c_double_p, c_int64_p]),

@@ -163,6 +163,7 @@ int gp_eval_driver(dfh_gp* gp, const EvalReq& rq);          // predict / acquisi
 int posterior_chunk(dfh_gp* gp, const double* Xs_dev, int64_t mc, int64_t ldxs, const ChunkReq& rq, double* mu_raw,
                     double* ss, double* ss2, ChunkOut* out = nullptr);
 int posterior_acq(dfh_ctx* ctx, const AcqArgs& a);
+int pointwise_variance_error();                              // sets the point-wise draw's message, returns DFH_ERR_JITTER
 // gp_halluc.hip
 int halluc_resolve(dfh_gp* gp, const double* Xh, int64_t q, HallucScope* s);
 // posterior_chunk with the scope's points in progress; *out is what hs.cov_gp()'s call left, `spare` takes hs.aug's own mean

@@ -1,5 +1,6 @@
 // Thompson sampling, the joint draw with points in progress and the multi-objective acquisitions (include/dfhip.h).
 #include "gp.h"
+#include "argmax.h"
 #include <algorithm>
 
 namespace {
@@ -118,7 +119,42 @@ __global__ void k_mo_scalarise(int scal, int ucb, int k, double beta, MoParams p
   out[i] = v;
 }
 
-// What both multi-objective entry points demand of their arguments (include/dfhip.h)
+// Point-wise multi-objective Thompson sampling (dfh_mo_ts_pointwise), all m candidates in one launch, one candidate per
+// thread: from objective j's posterior mean MU[j * ld + i] and unclipped standard deviation SD[j * ld + i]
+// (k_posterior_acq's) and the normal U[i * k + j] -- POINT-major, the order the reference's loops draw them in -- the
+// one-point draw s = sd u + mu of k_ts_pointwise (product and sum rounded apart), written to S[j * ld + i] where wanted;
+// the k draws scalarised in registers by k_mo_scalarise's TS formulas, in its order; then the first stage of the arg-max,
+// one partial winner per workgroup (argmax_finish does the rest).  *bad is set when some sd is not > 0 (NaN included),
+// where the reference's 1 x 1 stable_cholesky fails on every rung of its ladder.
+__global__ __launch_bounds__(256) void k_mo_ts_pointwise(
+    int scal, int k, MoParams par, const double* __restrict__ MU, const double* __restrict__ SD, long ld,
+    const double* __restrict__ U, long m, double* __restrict__ S, double* __restrict__ vals, double* __restrict__ pv,
+    long* __restrict__ pi, int* __restrict__ bad) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  double bv = -INFINITY; long bi = ARGMAX_NONE;
+  int not_pd = 0;
+  if (i < m) {
+    double v = scal == DFH_MO_LIN ? 0.0 : INFINITY;            // :33 / :58
+    for (int j = 0; j < k; ++j) {
+      const double sd = SD[j * ld + i];
+      not_pd |= !(sd > 0.0);
+      const double s = sd * U[i * k + j] + MU[j * ld + i];
+      if (S) S[j * ld + i] = s;
+      if (scal == DFH_MO_LIN) v = v + s * par.w[j];            // :38
+      else v = np_minimum(v, (s - par.ref[j]) / par.w[j]);     // :64
+    }
+    bv = v; bi = i;
+    vals[i] = v;
+  }
+  not_pd = __syncthreads_or(not_pd);
+  block_argmax(bv, bi);
+  if (threadIdx.x == 0) {
+    pv[blockIdx.x] = bv; pi[blockIdx.x] = bi;
+    if (not_pd) atomicOr(bad, 1);
+  }
+}
+
+// What the multi-objective entry points demand of their arguments (include/dfhip.h)
 int mo_check(dfh_gp* const* gps, int32_t k, int scal, const double* weights, const double* refs, MoParams* par) {
   DFH_ARG(gps && k >= 1 && k <= DFH_MO_MAX_OBJECTIVES && weights);
   DFH_ARG(scal == DFH_MO_LIN || scal == DFH_MO_TCH);
@@ -574,5 +610,65 @@ extern "C" int dfh_mo_ts_argmax(dfh_gp* const* gps, int32_t k, int scal, const d
   if (vals_out) DFH_TRY(from_device(ctx, vals_out, vals, (size_t)m * 8));
   DFH_HIP(hipStreamSynchronize(ctx->stream));
   best.store(best_val, best_idx);
+  return DFH_OK;
+}
+
+// mo_lin_asy_ts / mo_tch_asy_ts on a Cartesian-product domain (include/dfhip.h): per objective the chunked posterior of
+// dfh_gp_ts_pointwise, its points in progress included, leaves mean and unclipped standard deviation; one launch of
+// k_mo_ts_pointwise then draws, scalarises and takes the first arg-max stage for all m candidates.
+extern "C" int dfh_mo_ts_pointwise(dfh_gp* const* gps, int32_t k, int scal, const double* weights, const double* refs,
+                                   const double* Xs, int64_t m, const double* Xh, int64_t q, const double* U,
+                                   const double* mean_consts, const double* mean_vals, double* samples_out,
+                                   double* vals_out, double* best_val, int64_t* best_idx) {
+  MoParams par;
+  DFH_TRY(mo_check(gps, k, scal, weights, refs, &par));
+  DFH_ARG(Xs && U && m >= 1 && q >= 0 && (q == 0 || Xh) && (mean_consts || mean_vals));
+  dfh_ctx* ctx = gps[0]->ctx;
+  DFH_HIP(hipSetDevice(ctx->device));
+  const int64_t d = gps[0]->d;
+  // candidates and normals (where they come from the host) | the K means | the K standard deviations | the K draws
+  // (where wanted) | the scalarised values.  Memory of this call's own, not scratch: the hallucination's fall-back
+  // re-fits a GP between two objectives.
+  DevBlock hold(ctx);
+  const size_t b_xs = is_device_ptr(Xs) ? 0 : (size_t)m * d * 8, b_u = is_device_ptr(U) ? 0 : (size_t)m * k * 8;
+  const size_t rows = 2 * (size_t)k + (samples_out ? (size_t)k : 0) + 1;
+  DFH_TRY(dev_alloc(ctx, b_xs + b_u + rows * m * 8, &hold.p));
+  char* hp = static_cast<char*>(hold.p);
+  if (b_xs) { DFH_HIP(hipMemcpyAsync(hp, Xs, b_xs, hipMemcpyHostToDevice, ctx->stream)); Xs = reinterpret_cast<const double*>(hp); }
+  if (b_u) { DFH_HIP(hipMemcpyAsync(hp + b_xs, U, b_u, hipMemcpyHostToDevice, ctx->stream)); U = reinterpret_cast<const double*>(hp + b_xs); }
+  if (b_xs + b_u) DFH_HIP(hipStreamSynchronize(ctx->stream));      // pageable sources: staged before the caller's buffers may change
+  double* MU = reinterpret_cast<double*>(hp + b_xs + b_u);
+  double* SD = MU + (int64_t)k * m;
+  double* S = samples_out ? SD + (int64_t)k * m : nullptr;
+  double* vals = SD + (int64_t)k * m * (samples_out ? 2 : 1);
+  for (int j = 0; j < k; ++j) {
+    // get_gp_sampler_for_parallel_strategy (:29, :54) per point: the posterior of the GP augmented with the points in
+    // progress, the mean from the real data (gp_core.py:256-261)
+    EvalReq rq;
+    rq.Xs = Xs; rq.m = m; rq.ldxs = d; rq.kxx = gps[j]->kd.kxx;
+    rq.Xh = Xh; rq.q = q;
+    rq.mean_const = mean_consts ? mean_consts[j] : 0.0;
+    rq.mean_vals = mean_vals ? mean_vals + (int64_t)j * m : nullptr;
+    rq.mu_out = MU + (int64_t)j * m; rq.sd_out = SD + (int64_t)j * m;
+    DFH_TRY(gp_eval_driver(gps[j], rq));
+  }
+  double hv = 0.0; int64_t hi = -1; int hbad = 0;
+  {
+    SectionTimer t(ctx, DFH_T_ACQ);
+    ArgmaxParts p;
+    const int nparts = (int)((m + 255) / 256);
+    DFH_TRY(argmax_parts(ctx, nparts, &p));
+    DFH_HIP(hipMemsetAsync(p.flag, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(k_mo_ts_pointwise, dim3((unsigned)nparts), dim3(256), 0, ctx->stream, scal, (int)k, par, (const double*)MU,
+                       (const double*)SD, (long)m, U, (long)m, S, vals, p.pv, p.pi, p.flag);
+    DFH_LAUNCH_CHECK();
+    DFH_TRY(argmax_finish(ctx, p, nparts, &hv, &hi, &hbad));      // winner and flag in one synchronisation
+  }
+  if (hbad) return pointwise_variance_error();
+  if (samples_out) DFH_TRY(from_device(ctx, samples_out, S, (size_t)k * m * 8));
+  if (vals_out) DFH_TRY(from_device(ctx, vals_out, vals, (size_t)m * 8));
+  DFH_HIP(hipStreamSynchronize(ctx->stream));
+  if (best_val) *best_val = hv;
+  if (best_idx) *best_idx = hi;
   return DFH_OK;
 }

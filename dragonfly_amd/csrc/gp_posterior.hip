@@ -143,6 +143,13 @@ __global__ __launch_bounds__(256) void k_ts_pointwise(
 
 }  // namespace
 
+// A one-point draw whose variance is not positive: the exhausted ladder of the reference's 1 x 1 stable_cholesky
+int pointwise_variance_error() {
+  dfh_set_error("Could not compute Cholesky decomposition of a candidate's 1 x 1 posterior covariance: the variance is "
+                "not positive. This is likely because the M is not positive semi-definite or has infinities/nans.");
+  return DFH_ERR_JITTER;
+}
+
 int posterior_acq(dfh_ctx* ctx, const AcqArgs& a) {
   hipLaunchKernelGGL(k_posterior_acq, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, ctx->stream, a.acq, a.p0, a.p1, a.kxx,
                      a.kss, a.mean_const, a.mean_vals, a.mu_raw, a.ss, a.ss2, (long)a.m, a.mu_out, a.sd_out, a.val_out);
@@ -239,11 +246,7 @@ int ts_epilogue(dfh_ctx* ctx, const EvalReq& rq, const ChunkVecs& v, const Chunk
     DFH_LAUNCH_CHECK();
     DFH_TRY(argmax_finish(ctx, p, nparts, &hv, &hi, &hbad));
   }
-  if (hbad) {
-    dfh_set_error("Could not compute Cholesky decomposition of a candidate's 1 x 1 posterior covariance: the variance is "
-                  "not positive. This is likely because the M is not positive semi-definite or has infinities/nans.");
-    return DFH_ERR_JITTER;
-  }
+  if (hbad) return pointwise_variance_error();
   best->merge(hv, hi);
   if (rq.vals_out) DFH_TRY(from_device(ctx, rq.vals_out + c.i0, v.val, (size_t)c.mc * 8));
   return DFH_OK;

@@ -606,6 +606,32 @@ class Engine(object):
       return bv.value, bi.value, vals, powers
     return bv.value, bi.value
 
+  def mo_thompson_pointwise(self, gps, scal, weights, refs, Xs, normals=None, X_halluc=None, mean_consts=None,
+                            mean_vals=None, return_vals=False, return_samples=False):
+    """ Point-wise multi-objective Thompson sampling (dfh_mo_ts_pointwise): per candidate and objective the one-point
+        draw of FittedGP.thompson_pointwise, the K draws of a candidate scalarised, and the arg-max, in one device call
+        -- what the reference's maximisers on Cartesian-product domains make of mo_lin_asy_ts / mo_tch_asy_ts.
+        normals: the m * K standard normals [m x K], POINT-major (host array or DeviceArray; mo_thompson's U is
+        objective-major); None: Engine.random_normals(m * K), which continues the global np.random stream exactly as
+        m * K calls of np.random.normal(size=(1, 1)) do.  A variance that is not positive raises the ValueError of an
+        exhausted jitter ladder.  Returns (best_val, best_idx[, vals][, samples [K x m]]). """
+    handles, k, scal_id, w, r, Xs, m, mc, mv = self._mo_args(gps, scal, weights, refs, Xs, mean_consts, mean_vals)
+    own = normals is None
+    Uh = self.random_normals(m * k) if own else (normals if isinstance(normals, DeviceArray) else _f64(np.ravel(normals)))
+    try:
+      if Uh.size != m * k:
+        raise ValueError('normals must hold one standard normal per candidate and objective.')
+      Xh, q = _halluc_rows(X_halluc)
+      vals = np.empty(m) if return_vals else None
+      samples = np.empty((k, m)) if return_samples else None
+      bv, bi = C.c_double(0), C.c_int64(-1)
+      check(self.lib.dfh_mo_ts_pointwise(handles, k, scal_id, _ptr(w), _ptr(r), _ptr(Xs), m, _ptr(Xh), q, _ptr(Uh), _ptr(mc),
+                                         _ptr(mv), _ptr(samples), _ptr(vals), C.byref(bv), C.byref(bi)))
+    finally:
+      if own:
+        Uh.free()
+    return (bv.value, bi.value) + ((vals,) if return_vals else ()) + ((samples,) if return_samples else ())
+
   # -- GP ----------------------------------------------------------------------------------
   def gp_lml_batch(self, specs, X, y, mean_consts, noise_vars, allow_jitter=True, return_powers=False,
                    handle_non_psd_kernels='guaranteed_psd'):

@@ -63,6 +63,12 @@ edited):
                K objectives' posteriors (or joint draws, points in progress hallucinated on the device), the
                scalarisation and the arg-max in one device call -- the reference's own callables elsewhere.
                Opt-in: without the flag the per-objective call stream of S4' stays exactly as it was.
+               With cartesian_product=True and cp_acquisitions=True as well, the four dispatchers call ours on
+               Cartesian-product domains too, when multiobjective_gpb_acquisitions.mo_cp_acquisition_applies holds: K
+               device CP GPs on the descriptor route on one engine, kernels guaranteed PSD, no multi-fidelity.  A
+               Thompson step is the reference's samples in ONE mo_thompson_pointwise call (dfh_mo_ts_pointwise, normals
+               point-major), a UCB step ONE mo_ucb_argmax on 'rand', a frontier per call under the tree search, one call
+               per point under Dragonfly's own maximisers (the GA, a compiled DIRECT).  The names rebound are the same.
   S4''' BOCA   (only with install(multi_fidelity=True, boca=True)) dragonfly.opt.gpb_acquisitions.boca (looked up
                at call time, opt/gp_bandit.py:495,660,663) -> a dispatcher: dragonfly_amd.gpb_acquisitions.boca when
                the GP is the mirror EuclideanMFGP with a device kernel on a Euclidean domain -- the point chosen by
@@ -93,8 +99,9 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
   """ Rebinds the names listed above; returns the list of patched attributes.
       boca=True (only together with multi_fidelity=True; ValueError otherwise): BOCA's decision step runs on the device.
       cp_acquisitions=True (only together with cartesian_product=True; ValueError otherwise): the S4 dispatchers call
-      ours on Cartesian-product domains too, where gpb_acquisitions.cp_acquisition_applies says so.  The names
-      rebound are the same with and without it.
+      ours on Cartesian-product domains too, where gpb_acquisitions.cp_acquisition_applies says so -- and, together
+      with multi_objective=True, the multi-objective dispatchers where
+      multiobjective_gpb_acquisitions.mo_cp_acquisition_applies does.  The names rebound are the same with and without it.
       tuning_gpus=N > 1 (with batched_tuning): a tuning batch large enough to fill more than one GPU
       (parallel.lml_shard_plan: more than 256 candidates up to n = 2047) is cut over N GPUs of this process
       (dfh_mgpu_lml_batch); every other batch, and everything with None or 1, goes exactly where it went before. """
@@ -156,7 +163,8 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
       ref_ns, our_ns = getattr(ref_moo_acq, ns_name), getattr(our_moo_acq, ns_name)
       for acq in ('lin_ts', 'tch_ts', 'lin_ucb', 'tch_ucb'):
         _saved.append((ref_ns, acq, getattr(ref_ns, acq)))
-        setattr(ref_ns, acq, _euclidean_dispatch(getattr(our_ns, acq), getattr(ref_ns, acq)))
+        setattr(ref_ns, acq, _euclidean_dispatch(getattr(our_ns, acq), getattr(ref_ns, acq),
+                                                 mo_cp_acq=acq if cp_acquisitions else None))
         patched.append('dragonfly.opt.multiobjective_gpb_acquisitions.%s.%s' % (ns_name, acq))
   if batched_tuning:
     import dragonfly.opt.gp_bandit as ref_gp_bandit
@@ -173,7 +181,7 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
   return patched
 
 
-def _euclidean_dispatch(ours, theirs, cp_acq=None):
+def _euclidean_dispatch(ours, theirs, cp_acq=None, mo_cp_acq=None):
   """ The acquisition entry installed in the reference's namespaces: ours on Euclidean domains,
       the reference's own callable on every other domain (Cartesian-product, neural-network, ...
       domains keep running exactly as before).  Works for asy (gp, anc_data) and syn
@@ -181,7 +189,10 @@ def _euclidean_dispatch(ours, theirs, cp_acq=None):
       cp_acq (install(cp_acquisitions=True): the acquisition's name): ours on a Cartesian-product domain as well,
       when gpb_acquisitions.cp_acquisition_applies holds for every GP of the call -- the device CP GP on the
       descriptor route with a kernel guaranteed PSD, no multi-fidelity, 'rand' or the tree search; the GA, a compiled
-      DIRECT, host-kernel GPs and add-UCB stay with the reference's callable. """
+      DIRECT, host-kernel GPs and add-UCB stay with the reference's callable.
+      mo_cp_acq (install(multi_objective=True, cartesian_product=True, cp_acquisitions=True): the multi-objective
+      acquisition's name): ours on a Cartesian-product domain when
+      multiobjective_gpb_acquisitions.mo_cp_acquisition_applies holds for the call's list of GPs. """
   def acquisition(*args, **kwargs):
     anc_data = args[-1]
     if isinstance(anc_data, (list, tuple)):
@@ -193,6 +204,10 @@ def _euclidean_dispatch(ours, theirs, cp_acq=None):
       gps = args[-2]
       gps = list(gps) if isinstance(gps, (list, tuple)) else [gps]
       if all(cp_acquisition_applies(cp_acq, gp, anc_data) for gp in gps):
+        return ours(*args, **kwargs)
+    if mo_cp_acq is not None and anc_data.domain.get_type() == 'cartesian_product':
+      from .multiobjective_gpb_acquisitions import mo_cp_acquisition_applies
+      if mo_cp_acquisition_applies(mo_cp_acq, args[-2], anc_data):
         return ours(*args, **kwargs)
     return theirs(*args, **kwargs)
   acquisition.__wrapped__ = ours

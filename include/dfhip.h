@@ -439,6 +439,31 @@ int dfh_mo_ts_argmax(dfh_gp* const* gps, int32_t k, int scal,
                      double* vals_out, double* best_val, int64_t* best_idx,
                      int32_t* jitter_powers_out /*[k x ceil(m/block)] or NULL*/);
 
+/* mo_lin_asy_ts / mo_tch_asy_ts on a Cartesian-product domain, where the reference's maximiser calls the closure one
+ * point at a time (opt/gpb_acquisitions.py:35-37, exd/exd_utils.py:265) and the closure draws once per objective:
+ * s_ij, candidate i and objective j, is the ONE-point draw that dfh_gp_ts_pointwise(gps[j], ...) makes from the
+ * normal U[i*k + j] -- sqrt(v) u + mu with v the unclipped posterior variance of row i alone, product and sum rounded
+ * apart; Xh hallucinated exactly as there (block form, or the augmented GP, always for fits with a projection flag).
+ * The k draws of a candidate are scalarised by the LIN TS / TCH TS formulas above, sums over j = 0 .. k-1, then the
+ * arg-max (first NaN, else first maximum).
+ * ORDER OF THE NORMALS: U is [m x k], POINT-major -- the reference's loop over points runs the loop over objectives
+ * inside it, each draw taking one np.random.normal(size=(1, 1)).  dfh_mo_ts_argmax above is OBJECTIVE-major ([k x m]):
+ * the two layouts are not interchangeable.
+ * samples_out: optional [k x m], objective-major (row j: objective j's draws); vals_out: optional [m].  Xs, U,
+ * mean_vals, samples_out and vals_out may be host or device pointers.  DFH_ERR_BAD_ARG, before any launch, for the
+ * conditions of the section's head, Gram-fitted handles, m < 1, q < 0, q > 0 without Xh, U == NULL, and neither
+ * mean_consts nor mean_vals.  DFH_ERR_JITTER (dfh_gp_ts_pointwise's message; outputs unspecified) if any objective's
+ * variance at any row is not > 0, NaN included: the reference's 1 x 1 stable_cholesky fails there on every rung. */
+int dfh_mo_ts_pointwise(dfh_gp* const* gps, int32_t k, int scal,
+                        const double* weights, const double* refs,
+                        const double* Xs, int64_t m,
+                        const double* Xh, int64_t q,            /* hallucinated points, may be NULL / 0 */
+                        const double* U /*[m x k], POINT-major: U[i*k + j]*/,
+                        const double* mean_consts, const double* mean_vals /*[k x m] objective-major, or NULL*/,
+                        double* samples_out /*[k x m] objective-major, or NULL*/,
+                        double* vals_out /*[m] or NULL*/,
+                        double* best_val, int64_t* best_idx);
+
 /* ---- candidate generation on the device ---------------------------------------------------
  * The m x d block of uniform candidates every random-search acquisition draws,
  *   np.random.random((max_evals, dim))                   (dragonfly/utils/oper_utils.py:62)
