@@ -31,6 +31,7 @@ import types
 
 from .gp_core import GP
 from .kernel import CartesianProductKernel
+from .mf_gp import MFGP
 
 
 def _uses_descriptor(self):
@@ -50,7 +51,48 @@ def _points_array(self, X):
   return self.kernel.pack(X)
 
 
+def _uses_mf_descriptor(self):
+  """ CPMFGP: the kernel is our mirror over exactly [fidel_space_kernel, domain_kernel] -- two product factors of
+      one descriptor (kernel.py: a part that is itself a product) --, every member has a device description, and no
+      member of either space is given by distances.  Then kernel_scale * KF * KD of the reference's training-matrix
+      hook (cartesian_product_gp.py:310-319) is the descriptor's value, rounding for rounding. """
+  kern = self.kernel
+  fidel_kernel, domain_kernel = getattr(self, 'fidel_space_kernel', None), getattr(self, 'domain_kernel', None)
+  if fidel_kernel is None or domain_kernel is None or not isinstance(kern, CartesianProductKernel):
+    return False
+  parts = kern.kernel_list
+  if len(parts) != 2 or parts[0] is not fidel_kernel or parts[1] is not domain_kernel or \
+     not all(isinstance(part, CartesianProductKernel) for part in parts) or \
+     kern.hyperparams['scale'] != self.kernel_scale:
+    return False
+  return kern.has_device_spec() and \
+         all(dists is None for dists in getattr(self, 'fidel_space_lists_of_dists', None) or []) and \
+         all(dists is None for dists in getattr(self, 'domain_lists_of_dists', None) or [])
+
+
+def _mf_generic(self):
+  """ gp_core.GP._generic for CPMFGP: host-kernel mode unless the GP runs from the descriptor. """
+  return not _uses_mf_descriptor(self)
+
+
+def _rebased_functions(ref_cls, env):
+  """ The functions (and class methods) of the reference class's body, re-made over the globals `env`. """
+  def remake(fn):
+    new = types.FunctionType(fn.__code__, env, fn.__name__, fn.__defaults__, fn.__closure__)
+    new.__kwdefaults__ = fn.__kwdefaults__
+    new.__doc__ = fn.__doc__
+    return new
+  body = {}
+  for name, fn in vars(ref_cls).items():
+    if isinstance(fn, types.FunctionType):
+      body[name] = remake(fn)
+    elif isinstance(fn, classmethod):
+      body[name] = classmethod(remake(fn.__func__))
+  return body
+
+
 _classes = {}      # reference module name -> the class made for it
+_mf_classes = {}   # the same for CPMFGP
 
 
 def device_cpgp_class(ref_module):
@@ -67,13 +109,38 @@ def device_cpgp_class(ref_module):
   env = dict(ref_module.__dict__)
   body = {'__doc__': ref_cls.__doc__, '__module__': __name__,
           '_generic': property(_generic), '_points_array': _points_array}
-  for name, fn in vars(ref_cls).items():
-    if isinstance(fn, types.FunctionType):
-      body[name] = types.FunctionType(fn.__code__, env, fn.__name__, fn.__defaults__, fn.__closure__)
-      body[name].__kwdefaults__ = fn.__kwdefaults__
-      body[name].__doc__ = fn.__doc__
+  body.update(_rebased_functions(ref_cls, env))
   cls = type('CPGP', (GP,), body)
   env['CPGP'] = cls
   _classes[ref_module.__name__] = cls
   globals()['CPGP'] = cls
+  return cls
+
+
+def is_device_cpmfgp(gp):
+  """ An instance of a class device_cpmfgp_class made. """
+  return any(isinstance(gp, cls) for cls in _mf_classes.values())
+
+
+def device_cpmfgp_class(ref_module):
+  """ The same recipe for the reference's CPMFGP (cartesian_product_gp.py:251-319), the multi-fidelity GP on a
+      Cartesian-product domain: its own function objects -- constructor, distance-list setters, string form, the
+      training-kernel-matrix hook and the class method behind it -- over dragonfly_amd.mf_gp.MFGP, one class per
+      reference module, published as CPMFGP of this module.  The constructor builds the joint kernel by the name
+      CartesianProductKernel: in the functions' globals that name is our mirror, so a GP made from
+      (kernel_scale, fidel_space_kernel, domain_kernel) mirrors gets the nested mirror and, when _uses_mf_descriptor
+      holds, runs from ONE product descriptor with two product factors; the joint points are (z, x) pairs, packed side
+      by side.  In every other case the hook puts the GP in host-kernel mode, as for CPGP. """
+  if ref_module.__name__ in _mf_classes:
+    return _mf_classes[ref_module.__name__]
+  ref_cls = ref_module.__dict__.get('_dfh_reference_CPMFGP', ref_module.CPMFGP)
+  env = dict(ref_module.__dict__)
+  env['CartesianProductKernel'] = CartesianProductKernel
+  body = {'__doc__': ref_cls.__doc__, '__module__': __name__,
+          '_generic': property(_mf_generic), '_points_array': _points_array}
+  body.update(_rebased_functions(ref_cls, env))
+  cls = type('CPMFGP', (MFGP,), body)
+  env['CPMFGP'] = cls
+  _mf_classes[ref_module.__name__] = cls
+  globals()['CPMFGP'] = cls
   return cls

@@ -252,11 +252,15 @@ struct PartDev {
   // CoordinateProductKernel: the multi-fidelity GP with an additive domain model, gp/euclidean_gp.py:696-707):
   // the factor's parts are adjacent; they are summed (0 + k_1 + k_2 ..., kernel.py:490-493), the sum is
   // scaled (kernel.py:494) and only then multiplied into the product (kernel.py:588).
-  int fmode;       // 0: a factor of its own ; FM_IN (| FM_BEGIN | FM_END): inside an additive factor
+  // A part of a PRODUCT FACTOR (FM_PROD: a CartesianProductKernel among the kernels of a CartesianProductKernel, the
+  // fidelity-space and domain kernels of a CPMFGP, gp/cartesian_product_gp.py:310-319): the factor's parts are
+  // adjacent; the factor starts at fscale * 1.0 (scale * np.ones, kernel.py:526), is multiplied by each part in turn
+  // (kernel.py:532) and multiplies the product at its last part.
+  int fmode;       // 0: a factor of its own ; FM_IN / FM_PROD (| FM_BEGIN | FM_END): inside an additive / a product factor
   int fpad;
-  double fscale;   // FM_END: the additive factor's scale
+  double fscale;   // the additive / product factor's scale (every part of the factor carries it)
 };
-constexpr int FM_IN = 4, FM_BEGIN = 1, FM_END = 2;
+constexpr int FM_IN = 4, FM_BEGIN = 1, FM_END = 2, FM_PROD = 8;
 constexpr int EXPDECAY_MAX_DIM = 8;
 constexpr int HAMMING_MAX_DIM = 32;    // one operand chunk of the kernel-matrix kernel (KM_KC); one level of NumPy's pairwise sum
 // where the weights of the Hamming columns sit in a kernel's device image (kerndev.hip: blob_layout), from its start
@@ -269,7 +273,7 @@ struct KernDev {
   int kind = 0, dim = 0, n_parts = 0, P = 0;
   bool multi = false;          // additive: sum over parts then outer scale; product: scale * prod over parts
   bool product = false;        // (multi only) combine the parts by multiplication (kernel.py:584-588)
-  bool nested = false;         // (product only) some factor is a sum of parts (PartDev::fmode)
+  bool nested = false;         // (product only) some factor is a sum or a product of parts (PartDev::fmode)
   double outer_scale = 1.0;
   std::vector<PartDev> parts;
   std::vector<int> cols;       // [P] source column per packed column (-1 = padding)

@@ -228,7 +228,7 @@ static int build_single_nonstationary(const dfh_kernel_desc* k, KernDev* kd) {
   return DFH_OK;
 }
 
-// additive / product kernels, a product's factors possibly additive themselves (nested)
+// additive / product kernels, a product's factors possibly additive or products themselves (nested)
 static int build_groups(const dfh_kernel_desc* k, KernDev* kd) {
   DFH_ARG(k->n_groups >= 1 && k->group_off && k->group_dims && k->sub_kind && k->sub_scale && k->sub_bw);
   const bool product = (k->kind == DFH_KERNEL_PRODUCT);
@@ -236,7 +236,7 @@ static int build_groups(const dfh_kernel_desc* k, KernDev* kd) {
   if (k->group_factor || k->factor_is_sum || k->factor_scale)
     DFH_ARG(product && k->group_factor && k->factor_is_sum && k->factor_scale);
   double acc = product ? k->scale : 0.0;
-  double facc = 0.0;                              // k(x, x) of the additive factor under way
+  double facc = 0.0;                              // k(x, x) of the additive / product factor under way
   for (int g = 0; g < k->n_groups; ++g) {
     const int lo = k->group_off[g], hi = k->group_off[g + 1];
     DFH_ARG(hi > lo);
@@ -256,7 +256,14 @@ static int build_groups(const dfh_kernel_desc* k, KernDev* kd) {
       DFH_ARG(f >= 0 && f <= g && (g == 0 ? f == 0 : (f == k->group_factor[g - 1] || f == k->group_factor[g - 1] + 1)));
       const bool first = g == 0 || k->group_factor[g - 1] != f;
       const bool last = g + 1 == k->n_groups || k->group_factor[g + 1] != f;
-      if (k->factor_is_sum[f]) {
+      if (k->factor_is_sum[f] == DFH_FACTOR_PRODUCT) {
+        // the groups of a Cartesian-product kernel: SE / Matern / exponential decay / Hamming (no polynomial, no factor inside)
+        DFH_ARG(kind_is_stationary(sk) || sk == DFH_KERNEL_EXPDECAY || sk == DFH_KERNEL_HAMMING);
+        pd.fmode = FM_PROD | (first ? FM_BEGIN : 0) | (last ? FM_END : 0);
+        pd.fscale = k->factor_scale[f];
+        facc = (first ? pd.fscale * 1.0 : facc) * k0;         // combine_nested's order
+        if (last) acc *= facc;
+      } else if (k->factor_is_sum[f]) {
         DFH_ARG(sk != DFH_KERNEL_EXPDECAY && sk != DFH_KERNEL_HAMMING);       // an additive kernel's groups: SE / Matern / polynomial
         pd.fmode = FM_IN | (first ? FM_BEGIN : 0) | (last ? FM_END : 0);
         pd.fscale = k->factor_scale[f];

@@ -188,9 +188,16 @@ __device__ __forceinline__ void hamming_eval(const double* w, int n, const doubl
 
 // One part's value into the running result of a product kernel whose factors may be sums of parts
 // (PartDev::fmode): a plain factor multiplies; inside an additive factor the parts are added up from
-// zero (np.zeros + k_1 + k_2 ..., kernel.py:490-493) and the scaled sum multiplies at its last part.
+// zero (np.zeros + k_1 + k_2 ..., kernel.py:490-493) and the scaled sum multiplies at its last part; inside a product
+// factor (FM_PROD) they multiply a running value that starts at the factor's scale (scale * np.ones, then *= k_1,
+// *= k_2 ..., kernel.py:526-532), and that value multiplies at its last part.  fsum is the factor under way.
 __device__ __forceinline__ void combine_nested(const PartDev& pd, double kv, double& res, double& fsum) {
   if (pd.fmode == 0) { res = res * kv; return; }
+  if (pd.fmode & FM_PROD) {
+    fsum = ((pd.fmode & FM_BEGIN) ? pd.fscale * 1.0 : fsum) * kv;
+    if (pd.fmode & FM_END) res = res * fsum;
+    return;
+  }
   fsum = (pd.fmode & FM_BEGIN) ? 0.0 + kv : fsum + kv;
   if (pd.fmode & FM_END) res = res * (pd.fscale * fsum);
 }

@@ -190,6 +190,8 @@ class KernelSpec(object):
       A product may hold ADDITIVE FACTORS (an AdditiveKernel among its kernels): list the factor's
       groups like any others and give group_factors[g] = index of the factor group g belongs to
       (non-decreasing), factor_sums[f] = True for an additive factor, factor_scales[f] = its scale.
+      factor_sums[f] = 2 (DFH_FACTOR_PRODUCT): the factor is itself a product, factor_scales[f] * k_g * k_g' ...
+      over its se / matern / expdecay / hamming groups (a CartesianProductKernel among the parts of one: CPMFGP).
       'esp' (ESPKernel, kernel.py:671-744): nu = order, one 1-D se / matern kernel per column in
       column order (sub_kinds / sub_scales / sub_nus / sub_bandwidths, one entry each; groups
       default to [[0], [1], ..]). """
@@ -269,7 +271,7 @@ class KernelSpec(object):
         if self.kind != 'product':
           raise ValueError('Additive factors exist in product kernels only.')
         gf = np.ascontiguousarray(self.group_factors, dtype=np.int32)
-        fs = np.ascontiguousarray([1 if s else 0 for s in self.factor_sums], dtype=np.int32)
+        fs = np.ascontiguousarray([int(s) for s in self.factor_sums], dtype=np.int32)     # 0 | 1 (True) | 2: a product factor
         fsc = _f64(self.factor_scales)
         if gf.size != ng or fs.size != fsc.size or (ng and int(gf.max()) >= fs.size):
           raise ValueError('group_factors / factor_sums / factor_scales do not fit the groups.')

@@ -21,9 +21,10 @@ step is the reference's own samples, packed in one pass, in ONE acq_argmax or (T
 candidate, not a joint draw) ONE thompson_pointwise call, and the tree search of an all-Euclidean product fetches its
 values a frontier per call.
 
-All three -- a Euclidean GP, BOCA's view of a multi-fidelity GP (FidelToOptGP), the device GP of a product domain -- take
+All four -- a Euclidean GP, BOCA's view of a multi-fidelity GP (FidelToOptGP), the device GP of a product domain, BOCA's
+view of the multi-fidelity GP of a product domain -- take
 the same fused step: _fused_source decides, before any random number is drawn, which of _euclidean_step / _boca_step /
-_cp_step describes it (a _FusedStep: handle, rows, prior mean, rows in progress, index -> point), and _fused_argmax or
+_cp_step / _cp_boca_step describes it (a _FusedStep: handle, rows, prior mean, rows in progress, index -> point), and _fused_argmax or
 _fused_thompson makes the one device call.  Add-UCB is one function (_add_ucb) over the handle's per-group and all-groups
 calls, BOCA's with the fidelity bound.  With DFH_GAP_LOG set every fused single-objective step records its margin.
 """
@@ -143,9 +144,14 @@ class FidelToOptGP(object):
     return self.mfgp.draw_samples_with_hallucinated_observations(n, self._joint(x), halluc_fidel_pts, *args, **kwargs)
 
   def is_fusable(self):
-    """ A Euclidean multi-fidelity mirror GP with a device kernel: its joint points are [z, x] rows. """
+    """ A Euclidean multi-fidelity mirror GP with a device kernel: its joint points are [z, x] rows.  Or the device
+        CPMFGP of a Cartesian-product domain on the descriptor route with a kernel guaranteed PSD (on_product_domain):
+        its joint points are (z, x) pairs, packed side by side. """
     from .mf_gp import EuclideanMFGP
-    return isinstance(self.mfgp, EuclideanMFGP) and _is_device_gp(self.mfgp)
+    return (isinstance(self.mfgp, EuclideanMFGP) and _is_device_gp(self.mfgp)) or self.on_product_domain()
+
+  def on_product_domain(self):
+    return _is_cp_device_mfgp(self.mfgp)
 
 def _fortran_direct_available():
   """ True when a Dragonfly with its compiled DIRECT is importable (oper_utils.py:21-25). """
@@ -279,6 +285,31 @@ def cp_acquisition_applies(acq, gp, anc_data):
   return acq == 'ts' or _cp_maximiser(anc_data) is not None
 
 
+def _is_cp_device_mfgp(mfgp):
+  """ The device CPMFGP (cartesian_product_gp.device_cpmfgp_class) running from the nested product descriptor, with a
+      kernel guaranteed positive semi-definite -- as _is_cp_device_step asks of a CPGP. """
+  from .cartesian_product_gp import is_device_cpmfgp
+  return is_device_cpmfgp(mfgp) and _is_device_gp(mfgp) and hasattr(mfgp.kernel, 'pack_many') and \
+         mfgp.kernel.is_guaranteed_psd()
+
+
+def cp_boca_applies(mfgp, anc_data):
+  """ Whether boca() of this module takes BOCA's decision step on a Cartesian-product domain: the device CPMFGP on the
+      descriptor route with a kernel guaranteed PSD.  Add-UCB is Euclidean-only in the reference and stays with it.
+      install(boca=True, cp_acquisitions=True, cp_multi_fidelity=True) asks before it calls ours. """
+  return anc_data.domain.get_type() == 'cartesian_product' and getattr(anc_data, 'curr_acq', None) != 'add_ucb' and \
+         _is_cp_device_mfgp(mfgp)
+
+
+def cp_boca_view_applies(acq, gp, anc_data):
+  """ Whether acquisition `acq` of this module serves BOCA's view of such a GP: the view boca() made (cp_boca_applies
+      held), and a maximiser of _cp_maximiser's two -- the GA and a compiled DIRECT keep the reference's callable, which
+      then evaluates point by point through the view. """
+  if acq not in ('ucb', 'ei', 'pi', 'ttei', 'ts') or not isinstance(gp, FidelToOptGP) or not gp.on_product_domain():
+    return False
+  return anc_data.domain.get_type() == 'cartesian_product' and (acq == 'ts' or _cp_maximiser(anc_data) is not None)
+
+
 class _BoxDomain(object):
   """ The Euclidean sub-domain of one additive group (EuclideanDomain(domain_bounds[group_j]),
       gpb_acquisitions.py:180). """
@@ -379,12 +410,31 @@ def _cp_step(gp, anc_data):
                     None if pts is None else gp.kernel.pack_many(pts), cands.__getitem__, pointwise=True)
 
 
+def _cp_boca_step(view, anc_data):
+  """ BOCA's view of the device CPMFGP of a product domain: the reference's samples packed by the domain kernel in one
+      pass and joined in HBM with the packed fidel_to_opt into rows of the joint descriptor; the prior mean is the joint
+      GP's on the (fidelity, point) pairs, the pairs in progress are packed jointly; the point is the winning sample. """
+  mfgp = view.mfgp
+  fitted = mfgp.device_gp
+  fidel_kernel, domain_kernel = mfgp.kernel.kernel_list
+  cands = _cp_candidates(anc_data)
+  joint = fitted.engine.join_fixed(fidel_kernel.pack([view.fidel_to_opt])[0], domain_kernel.pack_many(cands))
+  mean = _prior_mean(mfgp.mean_func, lambda: view._joint(cands))      # pylint: disable=protected-access
+  pts = _in_progress(anc_data)
+  return _FusedStep(fitted, joint, mean, None if pts is None else mfgp.kernel.pack_many(pts), cands.__getitem__,
+                    pointwise=True)
+
+
 def _fused_source(gp, anc_data, thompson=False):
-  """ Which of the three builds this step's _FusedStep, or None for the reference's closure route; decided before any
+  """ Which of the four builds this step's _FusedStep, or None for the reference's closure route; decided before any
       random number is drawn.  The fused call needs a device kernel and the 'rand' maximiser.  In a multi-fidelity run
       only BOCA's own view of a device GP is fused -- though Thompson sampling (thompson=True) has never asked a plain
       Euclidean GP whether the run is multi-fidelity.  Thompson sampling also needs a handle that draws the way the step
       asks: with the points in progress in one call (FittedGP.fused_draws), or point-wise on a product domain. """
+  if isinstance(gp, FidelToOptGP) and gp.on_product_domain():
+    if not (anc_data.domain.get_type() == 'cartesian_product' and _cp_maximiser(anc_data) == 'rand'):
+      return None
+    return _cp_boca_step if not thompson or hasattr(gp.mfgp.device_gp, 'thompson_pointwise') else None
   if isinstance(gp, FidelToOptGP):
     if not (_is_rand_euclidean(anc_data) and gp.is_fusable()):
       return None

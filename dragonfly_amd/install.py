@@ -35,6 +35,14 @@ edited):
                the same reason as the MF GP.  With batched_tuning, dragonfly.opt.gp_bandit.CPGPFitter and
                dragonfly.opt.multiobjective_gp_bandit.CPGPFitter -> make_batched_cp_fitter(...): the S3 fitter's
                batch objective for CP candidates, one dfh_gp_lml_batch call with the projection flag.
+  S2''' CP MF GP  (only with install(multi_fidelity=True, cartesian_product=True, cp_multi_fidelity=True))
+               dragonfly.gp.cartesian_product_gp.CPMFGP -> dragonfly_amd.cartesian_product_gp.device_cpmfgp_class(...):
+               the reference's own class body over dragonfly_amd.mf_gp.MFGP.  The joint kernel
+               kernel_scale * (1.0 * k_f1 * ..) * (1.0 * k_d1 * ..) is ONE product descriptor whose two factors are
+               products themselves (factor_is_sum = DFH_FACTOR_PRODUCT), multiplied on the device in the reference's
+               order; the (z, x) pairs are packed side by side.  Distance lists or a part the device does not know:
+               host-kernel mode, as for CPGP.  With batched_tuning dragonfly.opt.gp_bandit.CPMFGPFitter -> the batched
+               CP fitter (one dfh_gp_lml_batch call with the projection flag per batch of candidates).
   S4 acquisitions  dispatchers are written into the namespaces
                dragonfly.opt.gpb_acquisitions.asy / syn / seq (looked up with getattr at
                dragonfly/opt/gp_bandit.py:490,510,651,681): the fused callables on Euclidean
@@ -75,6 +83,13 @@ edited):
                the fused call on [fidel_to_opt, candidate] rows joined in HBM (add-UCB: dfh_mf_add_ucb_all on the
                joint GP's factor), the fidelity by the reference's rule over one eval_at_fidel call -- the
                reference's own boca otherwise.  Opt-in: without the flag the call stream of S2' stays as it was.
+  S4-CP-BOCA   (only with install(multi_fidelity=True, cartesian_product=True, boca=True, cp_acquisitions=True,
+               cp_multi_fidelity=True)) the BOCA dispatcher calls ours on Cartesian-product domains too, where
+               gpb_acquisitions.cp_boca_applies holds.  The point: the reference's samples packed by the domain kernel,
+               joined in HBM with the packed fidel_to_opt, the (fidelity, point) pairs in progress packed jointly, in
+               ONE acq_argmax / thompson_pointwise call; the tree search of an all-Euclidean domain a frontier per call
+               through the view; the GA, a compiled DIRECT and add-UCB the reference's callables, point by point on the
+               device posterior.  The fidelity: one eval_at_fidel call and the reference's rule.
   S4-CP        (only with install(cartesian_product=True, cp_acquisitions=True)) the S4 dispatchers of ucb / ei / pi / ttei / ts
                call ours on Cartesian-product domains as well, when gpb_acquisitions.cp_acquisition_applies holds: the device
                CP GP on the descriptor route, a kernel guaranteed PSD, no multi-fidelity, and 'rand' -- the reference's own
@@ -95,13 +110,17 @@ _saved = []     # (object, attribute name, original value)
 
 
 def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, multi_objective=False, tuning_gpus=None,
-            boca=False, cp_acquisitions=False):
+            boca=False, cp_acquisitions=False, cp_multi_fidelity=False):
   """ Rebinds the names listed above; returns the list of patched attributes.
       boca=True (only together with multi_fidelity=True; ValueError otherwise): BOCA's decision step runs on the device.
       cp_acquisitions=True (only together with cartesian_product=True; ValueError otherwise): the S4 dispatchers call
       ours on Cartesian-product domains too, where gpb_acquisitions.cp_acquisition_applies says so -- and, together
       with multi_objective=True, the multi-objective dispatchers where
       multiobjective_gpb_acquisitions.mo_cp_acquisition_applies does.  The names rebound are the same with and without it.
+      cp_multi_fidelity=True (only together with cartesian_product=True and multi_fidelity=True; ValueError otherwise):
+      dragonfly.gp.cartesian_product_gp.CPMFGP -> cartesian_product_gp.device_cpmfgp_class(...), the multi-fidelity GP
+      of Cartesian-product domains on the device GP, and with batched_tuning dragonfly.opt.gp_bandit.CPMFGPFitter ->
+      the batched CP fitter over it.  Without the flag neither name is touched.
       tuning_gpus=N > 1 (with batched_tuning): a tuning batch large enough to fill more than one GPU
       (parallel.lml_shard_plan: more than 256 candidates up to n = 2047) is cut over N GPUs of this process
       (dfh_mgpu_lml_batch); every other batch, and everything with None or 1, goes exactly where it went before. """
@@ -109,6 +128,9 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
     raise ValueError('install(boca=True) needs multi_fidelity=True: BOCA runs on the device through the mirror MF GP.')
   if cp_acquisitions and not cartesian_product:
     raise ValueError('install(cp_acquisitions=True) needs cartesian_product=True: the fused calls run on the device CP GP.')
+  if cp_multi_fidelity and not (cartesian_product and multi_fidelity):
+    raise ValueError('install(cp_multi_fidelity=True) needs cartesian_product=True and multi_fidelity=True: the '
+                     'multi-fidelity GP of product domains runs on the device CP kernel mirrors.')
   import dragonfly.gp.kernel as ref_kernel
   import dragonfly.gp.euclidean_gp as ref_egp
   import dragonfly.opt.gpb_acquisitions as ref_acq
@@ -134,6 +156,8 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
     for name in ('HammingKernel', 'CartesianProductKernel'):
       _set(ref_kernel, name, getattr(kernel, name))
       _set(ref_cpgp, name, getattr(kernel, name))
+    if cp_multi_fidelity:
+      _set(ref_cpgp, 'CPMFGP', cartesian_product_gp.device_cpmfgp_class(ref_cpgp))
   for ns_name in ('asy', 'syn', 'seq'):
     ref_ns = getattr(ref_acq, ns_name)
     our_ns = getattr(gpb_acquisitions, ns_name)
@@ -144,7 +168,8 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
       patched.append('dragonfly.opt.gpb_acquisitions.%s.%s' % (ns_name, acq))
   gpb_acquisitions.external_maximise_with_method = maximise_with_method
   if boca:
-    _set(ref_acq, 'boca', _boca_dispatch(gpb_acquisitions.boca, ref_acq.boca))
+    _set(ref_acq, 'boca', _boca_dispatch(gpb_acquisitions.boca, ref_acq.boca,
+                                         cp_boca=cp_acquisitions and cp_multi_fidelity))
   # the multi-objective acquisitions (opt/multiobjective_gpb_acquisitions.py:19-107) are closures
   # over rows of points handed to maximise_acquisition, a name they import at module level: with
   # ours they get the batched tree search / vectorised random search on Euclidean domains
@@ -178,6 +203,9 @@ def install(multi_fidelity=False, batched_tuning=True, cartesian_product=False, 
       batched_cp = make_batched_cp_fitter(ref_cpgp.CPGPFitter, tuning_gpus=tuning_gpus)
       _set(ref_gp_bandit, 'CPGPFitter', batched_cp)
       _set(ref_moo_bandit, 'CPGPFitter', batched_cp)
+      if cp_multi_fidelity:
+        _set(ref_gp_bandit, 'CPMFGPFitter', make_batched_cp_fitter(ref_cpgp.CPMFGPFitter, tuning_gpus=tuning_gpus,
+                                                                   gp_name='CPMFGP', stand_in=_CPMFKernelMeanNoise))
   return patched
 
 
@@ -200,10 +228,11 @@ def _euclidean_dispatch(ours, theirs, cp_acq=None, mo_cp_acq=None):
     if anc_data.domain.get_type() == 'euclidean':
       return ours(*args, **kwargs)
     if cp_acq is not None and anc_data.domain.get_type() == 'cartesian_product':
-      from .gpb_acquisitions import cp_acquisition_applies
+      from .gpb_acquisitions import cp_acquisition_applies, cp_boca_view_applies
       gps = args[-2]
       gps = list(gps) if isinstance(gps, (list, tuple)) else [gps]
-      if all(cp_acquisition_applies(cp_acq, gp, anc_data) for gp in gps):
+      # (BOCA's view of a product-domain GP exists only where _boca_dispatch let our boca() make it)
+      if all(cp_acquisition_applies(cp_acq, gp, anc_data) or cp_boca_view_applies(cp_acq, gp, anc_data) for gp in gps):
         return ours(*args, **kwargs)
     if mo_cp_acq is not None and anc_data.domain.get_type() == 'cartesian_product':
       from .multiobjective_gpb_acquisitions import mo_cp_acquisition_applies
@@ -215,13 +244,18 @@ def _euclidean_dispatch(ours, theirs, cp_acq=None, mo_cp_acq=None):
   return acquisition
 
 
-def _boca_dispatch(ours, theirs):
+def _boca_dispatch(ours, theirs, cp_boca=False):
   """ dragonfly.opt.gpb_acquisitions.boca under install(boca=True): ours for the mirror EuclideanMFGP with a device
-      kernel on a Euclidean domain, the reference's own boca for everything else. """
+      kernel on a Euclidean domain, the reference's own boca for everything else.
+      cp_boca (install(boca=True, cp_acquisitions=True, cp_multi_fidelity=True)): ours on a Cartesian-product domain as
+      well, where gpb_acquisitions.cp_boca_applies holds -- the device CPMFGP on the descriptor route, a kernel
+      guaranteed PSD, not add-UCB. """
   def boca(select_pt_func, mfgp, anc_data, func_caller):
     from . import gpb_acquisitions, mf_gp
     if anc_data.domain.get_type() == 'euclidean' and isinstance(mfgp, mf_gp.EuclideanMFGP) and \
        gpb_acquisitions._is_device_gp(mfgp):     # pylint: disable=protected-access
+      return ours(select_pt_func, mfgp, anc_data, func_caller)
+    if cp_boca and gpb_acquisitions.cp_boca_applies(mfgp, anc_data):
       return ours(select_pt_func, mfgp, anc_data, func_caller)
     return theirs(select_pt_func, mfgp, anc_data, func_caller)
   boca.__wrapped__ = ours
@@ -583,14 +617,40 @@ class _CPKernelMeanNoise(object):
                             all(dists is None for dists in domain_lists_of_dists or []))
 
 
-def make_batched_cp_fitter(ref_fitter_cls, tuning_gpus=None):
+class _CPMFKernelMeanNoise(object):
+  """ The same with CPMFGP's constructor signature (gp/cartesian_product_gp.py:254-258): the joint kernel is composed
+      as that constructor composes it, from our mirror. """
+  __slots__ = ('kernel', 'mean_func', 'noise_var', 'handle_non_psd_kernels', 'host_kernel')
+
+  def __init__(self, ZZ, XX, YY, mf_kernel, mean_func, noise_var, kernel_scale=None, fidel_space_kernel=None,
+               domain_kernel=None, fidel_space_lists_of_dists=None, domain_lists_of_dists=None, build_posterior=True,
+               reporter=None, handle_non_psd_kernels='project_first'):
+    # pylint: disable=unused-argument
+    if build_posterior:
+      raise RuntimeError('dragonfly_amd.install: the candidate stand-in was asked for a real GP')
+    from .kernel import CartesianProductKernel
+    described = mf_kernel is None and isinstance(fidel_space_kernel, CartesianProductKernel) and \
+                isinstance(domain_kernel, CartesianProductKernel)
+    if described:
+      mf_kernel = CartesianProductKernel(kernel_scale, [fidel_space_kernel, domain_kernel])
+    self.kernel, self.mean_func, self.noise_var = mf_kernel, mean_func, noise_var
+    self.handle_non_psd_kernels = handle_non_psd_kernels
+    # (cartesian_product_gp._uses_mf_descriptor)
+    self.host_kernel = not (described and mf_kernel.has_device_spec() and
+                            all(dists is None for dists in fidel_space_lists_of_dists or []) and
+                            all(dists is None for dists in domain_lists_of_dists or []))
+
+
+def make_batched_cp_fitter(ref_fitter_cls, tuning_gpus=None, gp_name='CPGP', stand_in=_CPKernelMeanNoise):
   """ A subclass of the reference's CPGPFitter (gp/cartesian_product_gp.py:322-377) whose maximum-likelihood tuners see
       their objective as a batch: the machinery of make_batched_fitter -- the vectorised random search for 'rand' and
       'rand_exp_sampling', the batched tree search for 'pdoo' and the 'direct' fall-back, the speculative slice sampler
       -- over a batch objective that takes (kernel, mean, noise) of every candidate from the reference's own build_gp
       through a stand-in for the GP constructor and evaluates the list in ONE dfh_gp_lml_batch call with the
       projection flag.  The points are packed once per data set (the category codes do not depend on the
-      hyper-parameters).  Candidates whose kernel has no device description take one fit each. """
+      hyper-parameters).  Candidates whose kernel has no device description take one fit each.
+      gp_name, stand_in: the module global the fitter constructs its GP by and the stand-in bound to it while the
+      candidates are decoded -- ('CPMFGP', _CPMFKernelMeanNoise) for the reference's CPMFGPFitter (:394-497). """
   from . import parallel
   from .engine import get_engine
   base = make_batched_fitter(ref_fitter_cls, tuning_gpus=tuning_gpus)
@@ -613,8 +673,8 @@ def make_batched_cp_fitter(ref_fitter_cls, tuning_gpus=None):
         return np.zeros((0,))
       user_mean = getattr(self.options, 'mean_func', None) is not None
       import dragonfly.gp.cartesian_product_gp as _ref_cpgp
-      saved_cls = _ref_cpgp.CPGP
-      _ref_cpgp.CPGP = _CPKernelMeanNoise
+      saved_cls = getattr(_ref_cpgp, gp_name)
+      setattr(_ref_cpgp, gp_name, stand_in)
       specs, means, noises, mode, first_kernel = [], [], [], None, None
       try:
         for i, cts in enumerate(cts_hps_list):
@@ -629,7 +689,7 @@ def make_batched_cp_fitter(ref_fitter_cls, tuning_gpus=None):
           means.append(float(gp.mean_func([self.X[0]])[0]))
           noises.append(float(gp.noise_var))
       finally:
-        _ref_cpgp.CPGP = saved_cls
+        setattr(_ref_cpgp, gp_name, saved_cls)
       if specs is None:
         # an arbitrary mean function, or a kernel the host evaluates: one fit per candidate
         return np.array([self._tuning_objective(c, list(dscr_hps[j]) if per_cand else list(dscr_hps),

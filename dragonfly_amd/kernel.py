@@ -581,6 +581,7 @@ class ESPKernelMatern(ESPKernel):
 
 # ---- categorical inputs and Cartesian-product domains ---------------------------------------------------------------
 HAMMING_DEVICE_MAX_DIM = 32        # csrc/common.h: HAMMING_MAX_DIM
+FACTOR_PRODUCT = 2                 # include/dfhip.h: DFH_FACTOR_PRODUCT, a factor_sums value
 
 
 def _engine_knows_hamming():
@@ -729,7 +730,15 @@ class CartesianProductKernel(Kernel):
   def is_guaranteed_psd(self):
     return all(kern.is_guaranteed_psd() for kern in self.kernel_list)
 
+  @staticmethod
+  def _product_factor(kern):
+    """ A CartesianProductKernel mirror among the parts: the fidelity-space and the domain kernel of a multi-fidelity
+        GP on a Cartesian-product domain (cartesian_product_gp.py:262-263).  Its point is a list of parts. """
+    return isinstance(kern, CartesianProductKernel)
+
   def _part_dim(self, kern):
+    if self._product_factor(kern):
+      return kern.part_offsets()[1]
     kind = _factor_kind(kern)
     if kind == 'hamming':
       return len(np.ravel(kern.hyperparams['dim_weights']))
@@ -737,7 +746,11 @@ class CartesianProductKernel(Kernel):
 
   def has_device_spec(self):
     for kern in self.kernel_list:
-      if CoordinateProductKernel._additive_factor(kern):
+      if self._product_factor(kern):
+        # one level: the members of a product factor are single kernels the device knows
+        if len(kern.kernel_list) == 0 or not all(_factor_kind(k) in self._factor_kinds for k in kern.kernel_list):
+          return False
+      elif CoordinateProductKernel._additive_factor(kern):
         if not all(_factor_kind(k) in AdditiveKernel._factor_kinds for k in kern.kernel_list):
           return False
       elif _factor_kind(kern) not in self._factor_kinds:
@@ -745,7 +758,7 @@ class CartesianProductKernel(Kernel):
     return len(self.kernel_list) > 0
 
   def part_offsets(self):
-    """ First column of every part in the packed matrix, and the total width. """
+    """ First column of every part in the packed matrix, and the total width (a product factor's parts side by side). """
     offs, at = [], 0
     for kern in self.kernel_list:
       offs.append(at)
@@ -758,12 +771,45 @@ class CartesianProductKernel(Kernel):
     return CoordinateProductKernel(total, self.hyperparams['scale'], self.kernel_list, coords)
 
   def to_spec(self, in_dim=None):
-    """ One DFH_KERNEL_PRODUCT over the packed columns: part j is the column group [offset_j, offset_j + dim_j). """
+    """ One DFH_KERNEL_PRODUCT over the packed columns: part j is the column group [offset_j, offset_j + dim_j).  A part
+        that is itself a product lists its members as groups of one factor with factor_sums = 2 (DFH_FACTOR_PRODUCT)
+        and factor_scales = its own scale; the device multiplies in the reference's order. """
     if not self.has_device_spec():
       raise TypeError('This Cartesian-product kernel has a part the device does not evaluate.')
     inner = self._as_coordinate_product()
     inner._factor_kinds = self._factor_kinds
-    return inner.to_spec(in_dim=None)
+    if not any(self._product_factor(kern) for kern in self.kernel_list):
+      return inner.to_spec(in_dim=None)
+    groups, kinds, scales, nus, bws, gfac, fsum, fscale = [], [], [], [], [], [], [], []
+    offs, total = self.part_offsets()
+    for f, (kern, off) in enumerate(zip(self.kernel_list, offs)):
+      if self._product_factor(kern):
+        sub_offs, _ = kern.part_offsets()
+        members = [(k, list(range(off + so, off + so + kern._part_dim(k)))) for k, so in zip(kern.kernel_list, sub_offs)]
+        allowed = self._factor_kinds
+        fsum.append(FACTOR_PRODUCT)
+        fscale.append(kern.hyperparams['scale'])
+      elif CoordinateProductKernel._additive_factor(kern):
+        cols = list(range(off, off + self._part_dim(kern)))
+        members = [(k, [cols[int(c)] for c in grp]) for k, grp in zip(kern.kernel_list, kern.groupings)]
+        allowed = AdditiveKernel._factor_kinds
+        fsum.append(1)
+        fscale.append(kern.hyperparams['scale'])
+      else:
+        members = [(kern, list(range(off, off + self._part_dim(kern))))]
+        allowed = self._factor_kinds
+        fsum.append(0)
+        fscale.append(1.0)
+      for k, cols in members:
+        kind = _factor_kind(k)
+        if kind not in allowed:
+          raise TypeError('%s on the device supports %s sub-kernels only, got %s.'
+                          % (type(self).__name__, '/'.join(allowed), type(k)))
+        scale, nu, per_col = _factor_fields(k, kind)
+        groups.append(cols); kinds.append(kind); scales.append(scale); nus.append(nu); bws.append(per_col)
+        gfac.append(f)
+    return KernelSpec('product', total, self.hyperparams['scale'], groups=groups, sub_kinds=kinds, sub_scales=scales,
+                      sub_nus=nus, sub_bandwidths=bws, group_factors=gfac, factor_sums=fsum, factor_scales=fscale)
 
   def pack(self, X, many=False):
     """ The reference's list-of-lists points as the dense n x d matrix of to_spec: Euclidean, integral and
@@ -774,7 +820,9 @@ class CartesianProductKernel(Kernel):
     for j, (kern, off) in enumerate(zip(self.kernel_list, offs)):
       part = [pt[j] for pt in X]
       width = self._part_dim(kern)
-      if _factor_kind(kern) == 'hamming':
+      if self._product_factor(kern):
+        block = kern.pack(part, many=many)               # the part of a point is itself a list of parts
+      elif _factor_kind(kern) == 'hamming':
         block = kern.pack_many(part) if many else kern.pack(part)
       else:
         block = np.asarray(part, dtype=np.float64).reshape((len(X), -1))

@@ -97,7 +97,16 @@ typedef struct dfh_kernel_desc {
    * groups are listed like any others, group_factor[g] (non-decreasing, 0 .. n_factors-1) says
    * which factor group g belongs to, and a factor f with factor_is_sum[f] != 0 is
    * factor_scale[f] * (k_g + k_g' + ...) over its groups (sub_scale[g] = the group kernels' own
-   * scales); a factor with factor_is_sum[f] == 0 has exactly one group and is that kernel.        */
+   * scales); a factor with factor_is_sum[f] == 0 has exactly one group and is that kernel.
+   * factor_is_sum[f] == DFH_FACTOR_PRODUCT: the factor is itself a product, a CartesianProductKernel
+   * among the kernels of a CartesianProductKernel (the fidelity-space and the domain kernel of a
+   * multi-fidelity GP on a Cartesian-product domain, gp/cartesian_product_gp.py:310-319).  It is
+   * (factor_scale[f] * 1.0) * k_g * k_g' * ... over its groups, left to right, and the value
+   * multiplies the running result where its last group ends -- the reference's scale * np.ones,
+   * K *= k per part, then K_outer *= K (kernel.py:525-533), rounding for rounding.  Its groups are
+   * SE, MATERN, EXPDECAY or HAMMING; a POLY group, an additive factor inside it or a further
+   * level of nesting is DFH_ERR_BAD_ARG.  The add-UCB entry points do not take such a kernel.      */
+#define DFH_FACTOR_PRODUCT 2
   const int32_t* group_factor;   /* [n_groups]                                               */
   const int32_t* factor_is_sum;  /* [n_factors]                                              */
   const double*  factor_scale;   /* [n_factors]                                              */
