@@ -105,6 +105,7 @@ struct dfh_ctx {
   // gemm_cond_thr) and the look-ahead tile order with its completion counters.
   const double* gemm_cond = nullptr; double gemm_cond_thr = 0.0;
   int* gemm_la_cnt = nullptr;
+  int64_t gemm_solo_launches = 0;   // launches of gemm_f64_solo_kernel since the context was created
   // per-launch HIP-event profile of the GEMM kernel (bench.py roofline numbers)
   bool gemm_prof = false;
   struct GemmRec { hipEvent_t e0, e1; double flops, bytes; int variant; };

@@ -18,6 +18,10 @@
 // The plain kernels flip the wave priority inside the chunk -- 1 for the MFMA group behind the barrier, 0 for
 // the group in front of it -- so that of the two waves of a SIMD the one that has just left its barrier has
 // the pipe and the one about to wait gives way (+2 % at K >= 2048; see gemm_tile and docs/NOTES_gemm_kloop.md).
+// Long-K NT products on whole tiles take a second form of the same tile instead, gemm_f64_solo_kernel: ONE workgroup
+// per CU, K in chunks of 32, every LDS and global access pinned between two MFMAs (gemm_tile_solo).  The "~10 %
+// slower" above is the chunk-of-16 loop at one workgroup per CU, whose loads, LDS writes and barrier stand between its
+// MFMA groups with nothing to cover them; the solo loop has no such group and is 1.7 - 3.8 % faster from K = 1024 on.
 //
 // MFMA f64 16x16x4 lane maps (cdna_hip_programming.md section 3):
 //   A operand : lane l holds A[i = l&15][k = l>>4]
@@ -47,6 +51,7 @@ template <int WT> struct Geo {
   static constexpr int NN_PASSES = BK / NN_ROWS;
 };
 
+constexpr int K_SOLO = 1024;           // gemm_f64: smallest K of a product that takes the solo kernel (never below 1024)
 constexpr unsigned COND_GRID = 64;     // workgroups of a conditional (usually no-op) launch
 
 #ifndef DFH_GEMM_GROUP_M
@@ -132,12 +137,149 @@ __device__ __forceinline__ bool map_tile_lookahead(const GemmArgs& p, int la_pad
   return true;
 }
 
+// ---------------------------------------------------------------------------------------
+// The "solo" K loop of the 128 x 128 NT tile: ONE workgroup per CU, so one wave per SIMD -- the four waves
+// of the workgroup are paced by nothing but each other -- and a loop in which no instruction group stands in
+// front of or between the MFMAs.  K goes in chunks of 32 through a double-buffered LDS image of row stride
+// 34 doubles (2 * 256 rows * 34 * 8 B = 139264 B); per chunk a wave issues 128 MFMAs, 64 ds_read_b64,
+// 16 global_load_dwordx4 and 16 ds_write_b128, every one of them pinned between two MFMAs:
+//   k-step s (16 MFMAs), MFMAs 0..7 : the eight fragment reads of k-step s + 1 (other register slot)
+//   k-steps 0, 1,        MFMAs 8..15: the 16 global loads of chunk c + 1
+//   k-steps 4, 5,        MFMAs 8..15: their 16 LDS writes into the other buffer (read last in chunk c - 1)
+//   k-step 7, behind MFMA 3         : the chunk's one barrier, then under MFMAs 4..11 the reads of k-step 0
+//                                     of chunk c + 1
+// The last chunk is peeled.  MFMA k-steps run in ascending k, four consecutive columns each, exactly as in the
+// chunk-of-16 loop of gemm_tile: a result is the same sum in the same order, bit for bit.
+// ---------------------------------------------------------------------------------------
+constexpr int SBK = 32;
+constexpr int SBKP = 34;                    // 2*(r*34+k) mod 64 is distinct over r<16,k<2 -> ds_read_b64 conflict free
+constexpr int SOLO_TILE = 128 * SBKP;       // doubles per operand stage
+constexpr int SOLO_SMEM_DOUBLES = 4 * SOLO_TILE;      // A[2], B[2]: 139264 B
+
+// STAMP (diagnostics build only): s_memtime around the barrier and around the whole chunk, summed per wave into
+// stamps[0] (barrier) and stamps[1] (chunks), stamps[5] = chunks stamped (all but the peeled one).
+template <bool STAMP>
+__device__ __forceinline__ void gemm_tile_solo(const double* __restrict__ A, long lda, const double* __restrict__ B, long ldb,
+                                               int m0, int n0, int nchunks, double4_t (&acc)[4][4], double* smem,
+                                               unsigned long long* stamps) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  // staging: 16 lanes per 32-column row, 16 rows per pass, 8 passes per operand
+  const int s_row = tid >> 4, s_col = (tid & 15) * 2;
+  const double* ga = A + (long)(m0 + s_row) * lda + s_col;
+  const double* gb = B + (long)(n0 + s_row) * ldb + s_col;
+  double* const wa = smem + s_row * SBKP + s_col;                    // A stage 0; stage 1 at + SOLO_TILE
+  double* const wb = wa + 2 * SOLO_TILE;
+  const double* const fra = smem + (wm * 64 + l15) * SBKP + l4;
+  const double* const frb = smem + 2 * SOLO_TILE + (wn * 64 + l15) * SBKP + l4;
+  double2_t ra[8], rb[8];
+  double fa[2][4], fb[2][4];
+
+  auto load_one = [&](int q) {        // q < 16: one global_load_dwordx4
+    if (q < 8) ra[q] = *reinterpret_cast<const double2_t*>(ga + (long)(16 * q) * lda);
+    else rb[q - 8] = *reinterpret_cast<const double2_t*>(gb + (long)(16 * (q - 8)) * ldb);
+  };
+  auto store_one = [&](int buf, int q) {      // q < 16: one ds_write_b128
+    if (q < 8) *reinterpret_cast<double2_t*>(wa + buf * SOLO_TILE + 16 * q * SBKP) = ra[q];
+    else *reinterpret_cast<double2_t*>(wb + buf * SOLO_TILE + 16 * (q - 8) * SBKP) = rb[q - 8];
+  };
+  auto read_one = [&](int buf, int s, int slot, int q) {     // q < 8: one ds_read_b64 of k-step s
+    if (q < 4) fa[slot][q] = fra[buf * SOLO_TILE + q * 16 * SBKP + 4 * s];
+    else fb[slot][q - 4] = frb[buf * SOLO_TILE + (q - 4) * 16 * SBKP + 4 * s];
+  };
+  auto mfma_one = [&](int slot, int i) {
+    acc[i >> 2][i & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[slot][i >> 2], fb[slot][i & 3], acc[i >> 2][i & 3], 0, 0, 0);
+  };
+
+  [[maybe_unused]] unsigned long long st_last = 0, st_chunk = 0, st_bar = 0, st_all = 0;
+  auto now = [&]() {
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long t = __builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+  };
+
+#pragma unroll
+  for (int q = 0; q < 16; ++q) load_one(q);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) store_one(0, q);
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 8; ++q) read_one(0, 0, 0, q);
+  if constexpr (STAMP) st_chunk = now();
+
+  for (int kc = 0; kc + 1 < nchunks; ++kc) {
+    const int buf = kc & 1;
+    ga += SBK; gb += SBK;
+    // k-steps 0..6 and the first four MFMAs of k-step 7
+#pragma unroll
+    for (int m = 0; m < 116; ++m) {
+      const int s = m >> 4, i = m & 15, slot = s & 1;
+      const bool rd = s < 7 && i < 8, ld = s < 2 && i >= 8, st = (s == 4 || s == 5) && i >= 8;
+      if (rd) read_one(buf, s + 1, slot ^ 1, i);
+      if (ld) load_one(8 * s + i - 8);
+      if (st) store_one(buf ^ 1, 8 * (s - 4) + i - 8);
+      mfma_one(slot, i);
+      if (rd) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     // one DS read,
+      if (ld) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);     // or one global load,
+      if (st) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);     // or one DS write ...
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);             // ... one MFMA
+    }
+    // (pinned on both sides: left alone, hipcc sinks the twelve MFMAs in front of the barrier behind it, and the barrier
+    //  then waits for the fragment reads issued just before)
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (STAMP) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      st_last = now();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      const unsigned long long t = now();
+      st_bar += t - st_last;
+      st_all += t - st_chunk;
+      st_chunk = t;
+    } else {
+      __syncthreads();
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 4; i < 16; ++i) {
+      if (i < 12) read_one(buf ^ 1, 0, 0, i - 4);
+      mfma_one(1, i);
+      if (i < 12) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    }
+  }
+  {
+    const int buf = (nchunks - 1) & 1;
+#pragma unroll
+    for (int m = 0; m < 128; ++m) {
+      const int s = m >> 4, i = m & 15, slot = s & 1;
+      const bool rd = s < 7 && i < 8;
+      if (rd) read_one(buf, s + 1, slot ^ 1, i);
+      mfma_one(slot, i);
+      if (rd) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    }
+  }
+  if constexpr (STAMP) {
+    if (lane == 0) {
+      stamps[0] = st_bar; stamps[1] = st_all;
+      stamps[2] = stamps[3] = stamps[4] = 0;
+      stamps[5] = (unsigned long long)(nchunks - 1);
+    }
+  }
+}
+
 // PRIO: the priority flips of the 128-tile K loop (plain kernels only: the factorisation's extended launches run
 // beside its latency-bound panel kernels and keep priority 0 throughout).
 // STAMP (diagnostics build only, gemm_f64_stamp_kernel below): s_memtime stamps around the pieces of the
 // 128-tile K loop, summed per wave into stamps[0..5]; every other instantiation compiles to the same code
 // with or without it.
-template <bool TRANSB, bool EDGE, int WT, bool EXT, bool PRIO = false, bool STAMP = false>
+// SOLO: the chunk-of-32 loop of gemm_tile_solo (above) in place of the K loop; tile map, C prologue and epilogues as ever.
+template <bool TRANSB, bool EDGE, int WT, bool EXT, bool PRIO = false, bool STAMP = false, bool SOLO = false>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& p, int tm, int tn, bool is_la, int* la_cnt, double* smem,
                                           unsigned long long* stamps = nullptr) {
   using G = Geo<WT>;
@@ -157,7 +299,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& p, int tm, int tn, boo
 
   int kend = p.K;
   if (p.flags & GEMM_KTRI_B) kend = min(p.K, n0 + BN);   // B[j][k] = 0 for k > j
-  const int nchunks = (kend + BK - 1) / BK;
+  const int nchunks = SOLO ? kend / SBK : (kend + BK - 1) / BK;
 
   // C enters through the accumulators when alpha = +-1 (the SYRK / TRSM-update case): the tile of
   // beta*C is loaded at kernel entry, in flight together with the first operand chunk, instead of
@@ -254,14 +396,17 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& p, int tm, int tn, boo
     }
   };
 
-  if (nchunks > 0) {
-    load_chunk(0);
-    store_chunk(0);
+  if constexpr (!SOLO) {
+    if (nchunks > 0) {
+      load_chunk(0);
+      store_chunk(0);
+    }
+    __syncthreads();
   }
-  __syncthreads();
 
   // Fragment registers for the two k-pairs of a chunk (a pair = two MFMA k-steps = 8 columns).
-  // Schedule per chunk c (one wave per SIMD, so nothing else hides a stall):
+  // Schedule per chunk c (within a wave nothing else hides a stall; the second workgroup of the CU, i.e. the other wave
+  // of the SIMD, is what fills the pipe meanwhile):
   //   global loads of chunk c+1 | LDS reads of pair 1 (chunk c) | 32 MFMAs on pair 0 |
   //   LDS writes of chunk c+1, barrier | LDS reads of pair 0 (chunk c+1) | 32 MFMAs on pair 1
   // so every LDS read has a 32-MFMA (~2000 cycle) shadow and the only exposed work between the
@@ -309,7 +454,10 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& p, int tm, int tn, boo
     }
   };
 
-  if (WT == 4) {
+  if constexpr (SOLO) {
+    static_assert(!TRANSB && !EDGE && WT == 4 && !EXT && !PRIO, "the solo loop is the plain NT 128-tile's");
+    gemm_tile_solo<STAMP>(A, p.lda, B, p.ldb, m0, n0, nchunks, acc, smem, stamps);
+  } else if (WT == 4) {
     if (nchunks > 0) read_frags(0, 0, 0);
     stamp(-1);
     for (int kc = 0; kc < nchunks; ++kc) {
@@ -448,7 +596,27 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_cond_kernel(GemmArgs p, GemmE
   }
 }
 
+// The solo form of the plain NT 128-tile kernel (gemm_tile_solo): one workgroup per CU -- its 139264 B of LDS see to
+// that -- priority 0 throughout.  Long-K products only (gemm_f64 decides): with nobody else on the CU a tile's prologue
+// and epilogue are exposed.
+template <bool EDGE = false>
+__global__ __launch_bounds__(256) void gemm_f64_solo_kernel(GemmArgs p) {
+  static_assert(!EDGE, "the solo kernel has no bounds-checked form");
+  __shared__ __attribute__((aligned(16))) double smem[SOLO_SMEM_DOUBLES];
+  int tm, tn;
+  map_tile(p, blockIdx.x, gridDim.x, tm, tn);
+  gemm_tile<false, EDGE, 4, false, false, false, true>(p, tm, tn, false, nullptr, smem);
+}
+
 #ifdef DFH_DEBUG_HOOKS
+// diagnostics: the solo kernel with its stamps (barrier, whole chunk); out[(tile * 4 + wave) * 8 + 0..5]
+__global__ __launch_bounds__(256) void gemm_f64_solo_stamp_kernel(GemmArgs p, unsigned long long* out) {
+  __shared__ __attribute__((aligned(16))) double smem[SOLO_SMEM_DOUBLES];
+  int tm, tn;
+  map_tile(p, blockIdx.x, gridDim.x, tm, tn);
+  gemm_tile<false, false, 4, false, false, true, true>(p, tm, tn, false, nullptr, smem,
+                                                      out + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8);
+}
 // diagnostics: the plain NT 128-tile kernel, with or without its priority flips, with the K loop's stamps; out[(tile * 4 + wave) * 8 + 0..5]
 template <bool PRIO>
 __global__ __launch_bounds__(256, 2) void gemm_f64_stamp_kernel(GemmArgs p, unsigned long long* out) {
@@ -460,16 +628,20 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_stamp_kernel(GemmArgs p, unsi
 }
 #endif
 
-template <bool TRANSB, bool EDGE, int WT, bool EXT = false>
+// SOLO: gemm_f64_solo_kernel in place of the plain NT 128-tile kernel.  Its LDS image is a static array (the code
+// object's metadata states the 139264 B), so there is no dynamic size to raise; it is booked in slot 0 like the kernel
+// it stands in for -- the same tile, the same throughput configuration.
+template <bool TRANSB, bool EDGE, int WT, bool EXT = false, bool SOLO = false>
 int launch(dfh_ctx* ctx, const GemmArgs& p, dim3 grid, const GemmExt* x = nullptr) {
+  static_assert(!SOLO || (!TRANSB && !EDGE && WT == 4 && !EXT), "solo: plain NT 128-tile launches only");
   static bool attr_set_dev[2][DFH_MAX_DEVICES] = {{false}, {false}};
   bool& attr_set = attr_set_dev[(EXT && x->la_cnt != nullptr) ? 1 : 0][ctx->device];
   const bool la = EXT && x->la_cnt != nullptr;
   const void* kern = !EXT ? reinterpret_cast<const void*>(gemm_f64_kernel<TRANSB, EDGE, WT>)
                           : (la ? reinterpret_cast<const void*>(gemm_f64_la_kernel<EDGE>)
                                 : reinterpret_cast<const void*>(gemm_f64_cond_kernel<EDGE>));
-  constexpr int smem = Geo<WT>::SMEM_BYTES;
-  if (!attr_set) {
+  constexpr int smem = SOLO ? 0 : Geo<WT>::SMEM_BYTES;
+  if (!SOLO && !attr_set) {
     DFH_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     attr_set = true;
   }
@@ -502,6 +674,9 @@ int launch(dfh_ctx* ctx, const GemmArgs& p, dim3 grid, const GemmExt* x = nullpt
   if constexpr (EXT) {
     if (la) hipLaunchKernelGGL(gemm_f64_la_kernel<EDGE>, grid, dim3(256), smem, ctx->stream, p, *x);
     else hipLaunchKernelGGL(gemm_f64_cond_kernel<EDGE>, grid, dim3(256), smem, ctx->stream, p, *x);
+  } else if constexpr (SOLO) {
+    hipLaunchKernelGGL(gemm_f64_solo_kernel<EDGE>, grid, dim3(256), 0, ctx->stream, p);
+    ++ctx->gemm_solo_launches;
   } else hipLaunchKernelGGL((gemm_f64_kernel<TRANSB, EDGE, WT>), grid, dim3(256), smem, ctx->stream, p);
   DFH_LAUNCH_CHECK();
   if (rec) DFH_HIP(hipEventRecord(rec->e1, ctx->stream));
@@ -509,7 +684,7 @@ int launch(dfh_ctx* ctx, const GemmArgs& p, dim3 grid, const GemmExt* x = nullpt
 }
 
 template <int WT>
-int dispatch(dfh_ctx* ctx, GemmArgs& p, int count, bool edge, const GemmExt* ext = nullptr) {
+int dispatch(dfh_ctx* ctx, GemmArgs& p, int count, bool edge, const GemmExt* ext = nullptr, bool solo = false) {
   constexpr int BM = Geo<WT>::BM, BN = Geo<WT>::BN;
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.N + BN - 1) / BN;
@@ -535,6 +710,9 @@ int dispatch(dfh_ctx* ctx, GemmArgs& p, int count, bool edge, const GemmExt* ext
   }
   if (p.flags & GEMM_TRANSB)
     return edge ? launch<true, true, WT>(ctx, p, grid) : launch<true, false, WT>(ctx, p, grid);
+  if constexpr (WT == 4) {
+    if (solo && !edge) return launch<false, false, 4, false, true>(ctx, p, grid);
+  }
   return edge ? launch<false, true, WT>(ctx, p, grid) : launch<false, false, WT>(ctx, p, grid);
 }
 
@@ -760,7 +938,14 @@ int gemm_f64(dfh_ctx* ctx, int flags, int64_t M, int64_t N, int64_t K, double al
     return gemm_f64(ctx, flags, M - M1, N, K, alpha, A + M1 * lda, lda, B, ldb, beta,
                     Cin ? Cin + M1 * ldcin : nullptr, ldcin, Cout + M1 * ldc, ldc, batch);
   }
-  return dispatch<4>(ctx, p, count, edge);
+  // The solo kernel (one workgroup per CU, chunks of 32): long-K NT products with a full wave of tiles.  DFH_GEMM_SOLO,
+  // read once per process: 0 never, 1 (default) by the rule here, 2 every product eligible but for K and the tile count
+  // (tests).  K_SOLO: the smallest K from which it measured faster than the two-workgroup kernel by more than the spread
+  // (docs/NOTES_gemm_kloop.md section 5); below it a tile's exposed prologue and epilogue cost more than the loop gains.
+  static const int solo_mode = env_int("DFH_GEMM_SOLO", 1);
+  const bool solo = solo_mode != 0 && !(flags & GEMM_TRANSB) && K >= SBK && (K % SBK) == 0 &&
+                    (solo_mode >= 2 || (t128 >= 256 && K >= K_SOLO));
+  return dispatch<4>(ctx, p, count, edge, nullptr, solo);
 }
 
 // Enable / disable per-launch event timing of the GEMM kernel and fetch the totals.
@@ -814,6 +999,12 @@ extern "C" int dfh_ctx_gemm_profile(dfh_ctx* ctx, int enable, double* stats_out)
   return DFH_OK;
 }
 
+extern "C" int dfh_ctx_gemm_solo_launches(dfh_ctx* ctx, int64_t* out) {
+  DFH_ARG(ctx != nullptr && out != nullptr);
+  *out = ctx->gemm_solo_launches;
+  return DFH_OK;
+}
+
 #ifdef DFH_DEBUG_HOOKS      // diagnostics: built only with `python -m dragonfly_amd.build --debug-hooks` (include/dfhip_debug.h)
 extern "C" int dfh_debug_gemm_stamps(dfh_ctx* ctx, int64_t M, int64_t N, int64_t K, const double* A, const double* B,
                                      double* Cd, int prio, double* out) {
@@ -832,7 +1023,10 @@ extern "C" int dfh_debug_gemm_stamps(dfh_ctx* ctx, int64_t M, int64_t N, int64_t
   constexpr int smem = Geo<4>::SMEM_BYTES;
   DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_stamp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
   DFH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_stamp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-  if (prio) hipLaunchKernelGGL(gemm_f64_stamp_kernel<true>, dim3((unsigned)ntiles), dim3(256), smem, ctx->stream, p, dev);
+  if (prio == 2) {      // the solo kernel: out[0] = barrier, out[1] = whole chunks, out[5] = chunks stamped (all but the peeled one)
+    DFH_ARG(K % SBK == 0);
+    hipLaunchKernelGGL(gemm_f64_solo_stamp_kernel, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, p, dev);
+  } else if (prio) hipLaunchKernelGGL(gemm_f64_stamp_kernel<true>, dim3((unsigned)ntiles), dim3(256), smem, ctx->stream, p, dev);
   else hipLaunchKernelGGL(gemm_f64_stamp_kernel<false>, dim3((unsigned)ntiles), dim3(256), smem, ctx->stream, p, dev);
   DFH_LAUNCH_CHECK();
   std::vector<unsigned long long> host(nwaves * 8);

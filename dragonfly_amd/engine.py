@@ -468,6 +468,12 @@ class Engine(object):
     return [dict(launches=int(arr[5 * v]), ms=arr[5 * v + 1], flop=arr[5 * v + 2], busy_ms=arr[5 * v + 3],
                  bytes=arr[5 * v + 4]) for v in range(8)]
 
+  def gemm_solo_launches(self):
+    """ Launches of the one-workgroup-per-CU form of the 128-tile NT GEMM kernel since the context was created. """
+    out = C.c_int64(0)
+    check(self.lib.dfh_ctx_gemm_solo_launches(self.ctx, C.byref(out)))
+    return int(out.value)
+
   # -- building blocks ---------------------------------------------------------------------
   def kernel_matrix(self, spec, X1, X2=None, diag_add=0.0, out=None):
     X1h = X1 if isinstance(X1, DeviceArray) else _f64(X1)

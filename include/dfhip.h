@@ -662,6 +662,10 @@ int dfh_ctx_counters(dfh_ctx* ctx, int64_t* out /* [4] */);
  * (0) further recording.                                                                        */
 int dfh_ctx_gemm_profile(dfh_ctx* ctx, int enable, double* stats_out /* [40] or NULL */);
 
+/* Launches of the one-workgroup-per-CU ("solo") form of the 128x128 NT GEMM kernel since the context was
+ * created (diagnostics; long-K products take it, see DFH_GEMM_SOLO in INTEGRATION.md section 6).  Kept on the host. */
+int dfh_ctx_gemm_solo_launches(dfh_ctx* ctx, int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

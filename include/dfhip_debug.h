@@ -34,7 +34,8 @@ int dfh_debug_lmlt_stamps(void* dev_buf);
  * stamped instantiation of the 128-tile NT kernel, with (prio != 0) or without its priority flips: out[0..4] = s_memtime
  * ticks (shader cycles), summed over all waves, spent in {loads out + LDS reads + MFMA group 0, what is left to wait of
  * the global loads, LDS writes until retired, barrier, LDS reads + MFMA group 1}; out[5] = chunks summed over the waves;
- * out[6] = waves (tools/dbg_gemm_stamps.py).                                                                            */
+ * out[6] = waves (tools/dbg_gemm_stamps.py).  prio = 2: the stamped solo kernel (one workgroup per CU, chunks of 32, K a
+ * multiple of 32): out[0] = barrier, out[1] = whole chunks, out[5] = chunks stamped (the peeled last one is not).        */
 int dfh_debug_gemm_stamps(dfh_ctx* ctx, int64_t M, int64_t N, int64_t K, const double* A, const double* B, double* C,
                           int prio, double* out);
 #ifdef __cplusplus

@@ -28,4 +28,11 @@ for M, N, K in shapes:
     for name, v in zip(NAMES, out[:5]):
       print('  %-40s %6.2f %%   %7.1f cycles per chunk' % (name, 100.0 * v / tot, v / max(out[5], 1)))
     sys.stdout.flush()
+  if K % 32 == 0:
+    # the solo kernel (one workgroup per CU, chunks of 32 = 128 MFMAs per wave): the barrier and the whole chunk only
+    for rep in range(2):
+      check(lib.dfh_debug_gemm_stamps(eng.ctx, M, N, K, A.ptr, B.ptr, Cd.ptr, 2, out))
+    print('%d x %d x %d, solo kernel: %d waves, %.0f stamped chunks per wave, %.1f shader cycles per chunk of 32, barrier %.1f cycles (%.2f %%)' % (
+      M, N, K, out[6], out[5] / out[6], out[1] / max(out[5], 1), out[0] / max(out[5], 1), 100.0 * out[0] / max(out[1], 1)))
+    sys.stdout.flush()
   A.free(); B.free(); Cd.free()
