@@ -34,16 +34,17 @@ from .kernel import CartesianProductKernel
 from .mf_gp import MFGP
 
 
-def _uses_descriptor(self):
-  """ The kernel is our mirror, every part has a device description, and no part is given by distances. """
-  kern = self.kernel
-  return isinstance(kern, CartesianProductKernel) and kern.has_device_spec() and \
-         all(dists is None for dists in getattr(self, 'domain_lists_of_dists', None) or [])
+def runs_from_descriptor(kernel, *lists_of_dists):
+  """ The kernel is our mirror, every part has a device description, and no part -- of any of the spaces whose
+      distance lists are given -- comes with pre-computed distances.  The one definition of "runs from the descriptor":
+      the GP classes below ask it of themselves, the batched fitters' stand-ins (batched_fitter.py) of a candidate. """
+  return isinstance(kernel, CartesianProductKernel) and kernel.has_device_spec() and \
+         all(dists is None for lists in lists_of_dists for dists in lists or [])
 
 
 def _generic(self):
   """ gp_core.GP._generic: host-kernel mode unless the GP runs from the descriptor. """
-  return not _uses_descriptor(self)
+  return not runs_from_descriptor(self.kernel, getattr(self, 'domain_lists_of_dists', None))
 
 
 def _points_array(self, X):
@@ -65,9 +66,8 @@ def _uses_mf_descriptor(self):
      not all(isinstance(part, CartesianProductKernel) for part in parts) or \
      kern.hyperparams['scale'] != self.kernel_scale:
     return False
-  return kern.has_device_spec() and \
-         all(dists is None for dists in getattr(self, 'fidel_space_lists_of_dists', None) or []) and \
-         all(dists is None for dists in getattr(self, 'domain_lists_of_dists', None) or [])
+  return runs_from_descriptor(kern, getattr(self, 'fidel_space_lists_of_dists', None),
+                              getattr(self, 'domain_lists_of_dists', None))
 
 
 def _mf_generic(self):

@@ -810,7 +810,7 @@ def gen_engine_traces():
       anything is written the run is checked against the same run WITHOUT install(): the same points, bit for bit
       (dragonfly/opt/gp_bandit.py:405-421, 490, 647-673; apis/opt.py:138).
       The traces record the call stream of the install() of THIS commit: any change to what dragonfly_amd sends through
-      the engine object (batching in slice_sampler.py, install.py, the mirrors) needs them re-recorded --
+      the engine object (batching in slice_sampler.py, batched_fitter.py, the mirrors) needs them re-recorded --
       tests/test_engine_traces_cpu.py::test_committed_trace_is_the_call_stream_of_this_tree re-records one and fails
       when the committed trace is stale. """
   scenarios = engine_trace_scenarios()

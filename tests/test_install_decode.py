@@ -1,4 +1,4 @@
-"""dragonfly_amd.install: the batched fitter's direct decode of a tuning candidate (install.py: _decode_candidates)
+"""dragonfly_amd.install: the batched fitter's direct decode of a tuning candidate (batched_fitter.py: _decode_candidates)
 against what the reference's own build_gp makes of the same vector (dragonfly/gp/gp_core.py:501-543,
 gp/euclidean_gp.py:325-339, 796-897) -- kernel description, constant mean and noise variance equal to the last bit,
 over the fitter options that change the layout of the hyper-parameter vector.  CPU, needs the reference tree."""

@@ -1,4 +1,4 @@
-"""Host Python of ONE density evaluation of the slice sampler under install() (dragonfly_amd/install.py: _post_logp_batch ->
+"""Host Python of ONE density evaluation of the slice sampler under install() (dragonfly_amd/batched_fitter.py: _post_logp_batch ->
 _lml_batch -> engine.gp_lml_batch), with the library call replaced by a no-op (tools/noop_lml_batch.c, built here with
 gcc): what the mirrors and the binding cost per call, without a GPU.  Needs the Dragonfly checkout."""
 import os, subprocess, sys, tempfile, time, warnings, ctypes as C
