@@ -165,6 +165,7 @@ SIGNATURES = {
   'dfh_ctx_counters': (C.c_int, [C.c_void_p, c_int64_p]),
   'dfh_ctx_gemm_profile': (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
   'dfh_ctx_gemm_solo_launches': (C.c_int, [C.c_void_p, c_int64_p]),
+  'dfh_ctx_solve_launches': (C.c_int, [C.c_void_p, c_int64_p]),
 }
 
 _lib = None

@@ -1039,7 +1039,7 @@ const CholSwitches& chol_switches() {
 
 int refine_steps(double delta) {
   const double tol = chol_switches().refine_tol;
-  // test hook (tests/test_gpu_refine_steps.py): every block takes this many steps whatever its inverse is like
+  // test hook (tests/trsolve_forced_check.py, started by tests/test_gpu_trsolve.py): every block takes this many steps whatever its inverse is like
   static const int forced = env_int("DFH_REFINE_FORCE_STEPS", -1);
   if (forced >= 0) return forced > 8 ? 8 : forced;
   if (!(delta > tol)) return 0;

@@ -106,6 +106,7 @@ struct dfh_ctx {
   const double* gemm_cond = nullptr; double gemm_cond_thr = 0.0;
   int* gemm_la_cnt = nullptr;
   int64_t gemm_solo_launches = 0;   // launches of gemm_f64_solo_kernel since the context was created
+  int64_t solve_launches[16] = {0}; // the solve layer's booking since the context was created (SolveCounter; dfh_ctx_solve_launches)
   // per-launch HIP-event profile of the GEMM kernel (bench.py roofline numbers)
   bool gemm_prof = false;
   struct GemmRec { hipEvent_t e0, e1; double flops, bytes; int variant; };
@@ -221,6 +222,21 @@ int gemm_f64(dfh_ctx* ctx, int flags, int64_t M, int64_t N, int64_t K, double al
              const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
              const double* Cin, int64_t ldcin, double* Cout, int64_t ldc,
              const GemmBatch* batch = nullptr);
+
+// What ran inside the triangular solves (dfh_ctx::solve_launches, in the order dfh_ctx_solve_launches reports): counted on
+// the host where the kernel is launched, so that a test can hold a case to the kernel it was written for.
+enum SolveCounter {
+  SOLVE_TRSV_BLK_FWD = 0,       // k_trsv_blk_fwd
+  SOLVE_TRSV_UPD_FWD8,          // k_trsv_upd_fwd<8>
+  SOLVE_TRSV_UPD_FWD2,          // k_trsv_upd_fwd<2>
+  SOLVE_TRSV_BLK_BWD,           // k_trsv_blk_bwd
+  SOLVE_TRSV_UPD_BWD16,         // k_trsv_upd_bwd<16>
+  SOLVE_TRSV_UPD_BWD64,         // k_trsv_upd_bwd<64>
+  SOLVE_TRSV_GENERAL_BLOCKS,    // 512-blocks solved by the general single-vector route (gemv_rows / gemv_cols)
+  SOLVE_REFINE_STEPS,           // refinement steps, one per step, block and solve (single-vector and row solves alike)
+  SOLVE_SKINNY_BASE,            // gemm_skinny_kernel<MT, SPLIT>, eight slots: <1>, <2>, then <4>, <8>, <16> each unsplit, split
+  SOLVE_COUNTERS = 16
+};
 
 // Few-row variant (m <= 256, K a multiple of 64, NT only): streams B once, see gemm_f64.hip.
 // Acopy (optional, 16-byte aligned rows, even ld): A is also copied there -- it must not overlap

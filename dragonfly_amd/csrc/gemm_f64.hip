@@ -843,6 +843,8 @@ int launch_skinny(dfh_ctx* ctx, const SkinnyArgs& p) {
   hipLaunchKernelGGL((gemm_skinny_kernel<MT, SPLIT>), dim3((unsigned)((p.N + cols - 1) / cols)), dim3(256),
                      sizeof(double) * 16 * MT * SK_LDA, ctx->stream, p);
   DFH_LAUNCH_CHECK();
+  constexpr int slot = MT == 1 ? 0 : MT == 2 ? 1 : (MT == 4 ? 2 : MT == 8 ? 4 : 6) + (SPLIT ? 1 : 0);
+  ++ctx->solve_launches[SOLVE_SKINNY_BASE + slot];
   return DFH_OK;
 }
 

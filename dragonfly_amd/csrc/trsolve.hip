@@ -161,14 +161,17 @@ static int trsv_fast_forward(dfh_ctx* ctx, const double* L, int64_t n, int64_t l
     hipLaunchKernelGGL(k_trsv_blk_fwd, dim3((unsigned)((w + 3) / 4)), dim3(256), 0, ctx->stream, inv + (c0 / NB) * NB * NB,
                        (int)w, r + c0, z + c0);
     DFH_LAUNCH_CHECK();
+    ++ctx->solve_launches[SOLVE_TRSV_BLK_FWD];
     if (below > 4 * NB) {
       hipLaunchKernelGGL(k_trsv_upd_fwd<8>, dim3((unsigned)((below + 31) / 32)), dim3(256), 0, ctx->stream,
                          L + (c0 + w) * ldl + c0, (long)ldl, (long)below, z + c0, r + c0 + w);
       DFH_LAUNCH_CHECK();
+      ++ctx->solve_launches[SOLVE_TRSV_UPD_FWD8];
     } else if (below > 0) {                            // a short panel: two rows per wave, four times the workgroups
       hipLaunchKernelGGL(k_trsv_upd_fwd<2>, dim3((unsigned)((below + 7) / 8)), dim3(256), 0, ctx->stream,
                          L + (c0 + w) * ldl + c0, (long)ldl, (long)below, z + c0, r + c0 + w);
       DFH_LAUNCH_CHECK();
+      ++ctx->solve_launches[SOLVE_TRSV_UPD_FWD2];
     }
   }
   return DFH_OK;
@@ -182,14 +185,17 @@ static int trsv_fast_backward(dfh_ctx* ctx, const double* L, int64_t n, int64_t 
     hipLaunchKernelGGL(k_trsv_blk_bwd<16>, dim3((unsigned)((w + 15) / 16)), dim3(64 * TRSV_BW), 0, ctx->stream, inv + b * NB * NB,
                        (int)w, r + c0, a + c0);
     DFH_LAUNCH_CHECK();
+    ++ctx->solve_launches[SOLVE_TRSV_BLK_BWD];
     if (c0 > 0 && c0 < 8 * NB) {                       // fewer than 64 workgroups of 64 columns: 16 columns each
       hipLaunchKernelGGL(k_trsv_upd_bwd<16>, dim3((unsigned)((c0 + 15) / 16)), dim3(64 * TRSV_BW), 0, ctx->stream, L + c0 * ldl,
                          (long)ldl, (int)w, (long)c0, a + c0, r);
       DFH_LAUNCH_CHECK();
+      ++ctx->solve_launches[SOLVE_TRSV_UPD_BWD16];
     } else if (c0 > 0) {
       hipLaunchKernelGGL(k_trsv_upd_bwd<64>, dim3((unsigned)((c0 + 63) / 64)), dim3(64 * TRSV_BW), 0, ctx->stream, L + c0 * ldl,
                          (long)ldl, (int)w, (long)c0, a + c0, r);
       DFH_LAUNCH_CHECK();
+      ++ctx->solve_launches[SOLVE_TRSV_UPD_BWD64];
     }
   }
   return DFH_OK;
@@ -229,10 +235,12 @@ int trsv_forward(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const do
     const double* Lbb = diag + (c0 / NB) * NB * NB;
     // x_i <- Linv_ii x_i
     DFH_TRY(gemv_rows(ctx, Mi, w, w, NB, x + c0, 1.0, nullptr, 0.0, tmp));
+    ++ctx->solve_launches[SOLVE_TRSV_GENERAL_BLOCKS];
     for (int s = 0; s < (refine ? refine[c0 / NB] : 0); ++s) {
       // res = b_i - L_ii x ; x += Linv_ii res
       DFH_TRY(gemv_rows(ctx, Lbb, w, w, NB, tmp, -1.0, x + c0, 1.0, res, true));
       DFH_TRY(gemv_rows(ctx, Mi, w, w, NB, res, 1.0, tmp, 1.0, tmp));
+      ++ctx->solve_launches[SOLVE_REFINE_STEPS];
     }
     DFH_HIP(hipMemcpyAsync(x + c0, tmp, (size_t)w * 8, hipMemcpyDeviceToDevice, ctx->stream));
     // x[i+1:] <- x[i+1:] - L[i+1:, i] x_i
@@ -265,10 +273,12 @@ int trsv_backward(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const d
     const double* Lbb = diag + b * NB * NB;
     // x_i <- Linv_ii^T x_i
     DFH_TRY(gemv_cols(ctx, Mi, w, w, NB, x + c0, 1.0, nullptr, 0.0, tmp));
+    ++ctx->solve_launches[SOLVE_TRSV_GENERAL_BLOCKS];
     for (int s = 0; s < (refine ? refine[b] : 0); ++s) {
       // res = b_i - L_ii^T x ; x += Linv_ii^T res
       DFH_TRY(gemv_cols(ctx, Lbb, w, w, NB, tmp, -1.0, x + c0, 1.0, res));
       DFH_TRY(gemv_cols(ctx, Mi, w, w, NB, res, 1.0, tmp, 1.0, tmp));
+      ++ctx->solve_launches[SOLVE_REFINE_STEPS];
     }
     DFH_HIP(hipMemcpyAsync(x + c0, tmp, (size_t)w * 8, hipMemcpyDeviceToDevice, ctx->stream));
     // x[:i] <- x[:i] - L[i, :i]^T x_i
@@ -324,6 +334,7 @@ int trsm_rows(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const doubl
         const double* Lbb = diag + (c0 / NB) * NB * NB;
         DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, -1.0, T, NB, Lbb, NB, 1.0, Kct + c0, ldk, R2, NB));
         DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, 1.0, R2, NB, Linv, NB, 1.0, T, NB, T, NB));
+        ++ctx->solve_launches[SOLVE_REFINE_STEPS];
       }
       if (skinny_update) {
         DFH_TRY(gemm_skinny_nt(ctx, m, rest, w, -1.0, T, NB, Lpanel, ldl, 1.0, Kct + c0 + w, ldk,
@@ -349,6 +360,7 @@ int trsm_rows(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, const doubl
       const double* Lbb = diag + (c0 / NB) * NB * NB;
       DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, -1.0, Kct + c0, ldk, Lbb, NB, 1.0, T, NB, R2, NB));
       DFH_TRY(gemm_f64(ctx, GEMM_KTRI_B, m, w, w, 1.0, R2, NB, Linv, NB, 1.0, Kct + c0, ldk, Kct + c0, ldk));
+      ++ctx->solve_launches[SOLVE_REFINE_STEPS];
     }
   }
   return DFH_OK;
@@ -377,7 +389,14 @@ int trsm_rows_backward(dfh_ctx* ctx, const double* L, int64_t n, int64_t ldl, co
       // R <- T - X L_bb (the residual of the right-hand side T, which stays) ; X <- X + R Linv
       DFH_TRY(gemm_f64(ctx, GEMM_TRANSB, m, w, w, -1.0, Bt + c0, ldb, diag + b * NB * NB, NB, 1.0, T, NB, R2, NB));
       DFH_TRY(gemm_f64(ctx, GEMM_TRANSB, m, w, w, 1.0, R2, NB, inv + b * NB * NB, NB, 1.0, Bt + c0, ldb, Bt + c0, ldb));
+      ++ctx->solve_launches[SOLVE_REFINE_STEPS];
     }
   }
+  return DFH_OK;
+}
+
+extern "C" int dfh_ctx_solve_launches(dfh_ctx* ctx, int64_t* out) {
+  DFH_ARG(ctx != nullptr && out != nullptr);
+  for (int i = 0; i < SOLVE_COUNTERS; ++i) out[i] = ctx->solve_launches[i];
   return DFH_OK;
 }

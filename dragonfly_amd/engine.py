@@ -17,6 +17,10 @@ from ._lib import (ACQ_EI, ACQ_MEAN, ACQ_PI, ACQ_STD, ACQ_TTEI, ACQ_UCB, GET_ALP
 MO_SCALARISATIONS = {'lin': _lib.MO_LIN, 'tch': _lib.MO_TCH}
 # dfh_ctx_counters out[2]: the route of the most recent kernel-matrix build (csrc/kernmat.h: KmRoute)
 KM_ROUTES = (None, 'sym', 'cross_lds', 'strip', 'strip_mean', 'symmulti', 'generic', 'esp', 'colw')
+# dfh_ctx_solve_launches out[16] (csrc/common.h: SolveCounter)
+SOLVE_COUNTERS = ('trsv_blk_fwd', 'trsv_upd_fwd8', 'trsv_upd_fwd2', 'trsv_blk_bwd', 'trsv_upd_bwd16', 'trsv_upd_bwd64',
+                  'trsv_general_blocks', 'refine_steps', 'skinny_1', 'skinny_2', 'skinny_4', 'skinny_4_split', 'skinny_8',
+                  'skinny_8_split', 'skinny_16', 'skinny_16_split')
 ACQ_IDS = {'mean': ACQ_MEAN, 'ucb': ACQ_UCB, 'ei': ACQ_EI, 'pi': ACQ_PI, 'ttei': ACQ_TTEI,
            'std': ACQ_STD}
 
@@ -473,6 +477,14 @@ class Engine(object):
     out = C.c_int64(0)
     check(self.lib.dfh_ctx_gemm_solo_launches(self.ctx, C.byref(out)))
     return int(out.value)
+
+  def solve_launches(self):
+    """ What the triangular solves launched since the context was created (dfh_ctx_solve_launches), by SOLVE_COUNTERS'
+        names: the four single-vector kernels with their update variants, the 512-blocks solved by the general
+        single-vector route, the refinement steps run, and each instantiation of the few-row GEMM. """
+    arr = (C.c_int64 * len(SOLVE_COUNTERS))()
+    check(self.lib.dfh_ctx_solve_launches(self.ctx, arr))
+    return {name: int(arr[i]) for i, name in enumerate(SOLVE_COUNTERS)}
 
   # -- building blocks ---------------------------------------------------------------------
   def kernel_matrix(self, spec, X1, X2=None, diag_add=0.0, out=None):

@@ -666,6 +666,17 @@ int dfh_ctx_gemm_profile(dfh_ctx* ctx, int enable, double* stats_out /* [40] or 
  * created (diagnostics; long-K products take it, see DFH_GEMM_SOLO in INTEGRATION.md section 6).  Kept on the host. */
 int dfh_ctx_gemm_solo_launches(dfh_ctx* ctx, int64_t* out);
 
+/* What the triangular solves launched since the context was created (diagnostics; kept on the host, counted where the
+ * kernel is launched).  out[16]:
+ *   [0] k_trsv_blk_fwd   [1] k_trsv_upd_fwd<8>   [2] k_trsv_upd_fwd<2>
+ *   [3] k_trsv_blk_bwd   [4] k_trsv_upd_bwd<16>  [5] k_trsv_upd_bwd<64>
+ *   [6] 512-blocks solved by the general single-vector route (odd leading dimension, or a block that is refined)
+ *   [7] refinement steps run: one per step, block and solve, single-vector and many-right-hand-side solves alike
+ *   [8 .. 15] launches of the few-row GEMM gemm_skinny_kernel<MT, SPLIT>: <1>, <2>, <4>, <4, split>, <8>, <8, split>,
+ *             <16>, <16, split>.
+ * The tests hold every triangular-solve case to the kernels it was written for with them.                          */
+int dfh_ctx_solve_launches(dfh_ctx* ctx, int64_t* out /* [16] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,14 @@ k_trsv_upd_bwd, round 6; solve_lower_triangular / solve_upper_triangular of drag
 GP.build_posterior uses them, gp_core.py:161-163) against scipy.linalg.solve_triangular: sizes around the 512-block edges
 and the kernels' own edges (a last block of 1 .. 511 rows, panels shorter than the 2048 rows from which the forward update
 takes eight rows per wave, fewer than 4096 columns where the backward update takes 16 columns per workgroup), both
-directions through the C-ABI's dfh_solve_triangular, and alpha of a fit against the oracle at the same sizes."""
+directions through the C-ABI's dfh_solve_triangular, and alpha of a fit against the oracle at the same sizes.
+
+Which route a size takes (trsv_fast_applies refuses an odd leading dimension, and ldl = n here): the kernels named above
+run at the even sizes only -- 2 and 512 (one block: k_trsv_blk_fwd / k_trsv_blk_bwd alone), 1000, 1024 and 1536 (with
+k_trsv_upd_fwd<2> and k_trsv_upd_bwd<16>), 3000 (the only size of the first table with k_trsv_upd_fwd<8>: 2488 rows below the first block) and, in the alpha test
+and only to its 1e-10, 2600 and 4608 (the only one with k_trsv_upd_bwd<64>, which needs 4096 columns before the block).  The
+odd sizes 1, 63, 511, 513, 1025, 2047, 2049, 2561, 4097, 5121 take the general route (gemv_rows / gemv_cols per block).
+tests/test_gpu_trsolve.py reaches each kernel on purpose and asserts with Engine.solve_launches() that it ran."""
 import numpy as np
 import pytest
 from scipy.linalg import solve_triangular
