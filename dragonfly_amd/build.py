@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, 'csrc')
 OBJ_DIR = os.path.join(HERE, 'csrc', '_obj')
 LIB_PATH = os.path.join(HERE, 'libdfhip.so')
 SOURCES = ['runtime.hip', 'gemm_f64.hip', 'kernmat.hip', 'km_generic.hip', 'km_sym.hip', 'km_strip.hip', 'km_esp.hip', 'km_pack.hip', 'kerndev.hip', 'chol.hip', 'trsolve.hip', 'api.hip', 'gp_fit.hip', 'gp_posterior.hip', 'gp_halluc.hip', 'gp_argmax.hip', 'gp_adducb.hip', 'gp_draw.hip', 'gp_mf.hip',
-           'lml.hip', 'lml_tiny.hip', 'rng.hip', 'mgpu.hip', 'psdproj.hip', 'mtjump.hip']
+           'lml.hip', 'lml_tiny.hip', 'lml_grad.hip', 'rng.hip', 'mgpu.hip', 'psdproj.hip', 'mtjump.hip']
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "factor64.h"), os.path.join(CSRC, "kerneval.h"), os.path.join(CSRC, "lml_wg.h"), os.path.join(CSRC, "lml.h"),
            os.path.join(CSRC, "gp.h"), os.path.join(CSRC, "argmax.h"), os.path.join(CSRC, "kernmat.h"),
            os.path.join(HERE, '..', 'include', 'dfhip.h')]

@@ -17,6 +17,7 @@ struct dfh_gp {
   double* inv = nullptr;         // [2][nblk][NB][NB]: inverses of the diagonal blocks of L, then clean copies of the blocks
   std::vector<int> refine;       // [nblk] refinement steps the solves take with each block (chol.hip: refine_steps)
   double* alpha = nullptr;       // [n]
+  double lml = 0.0;              // log marginal likelihood of the fit (gp_core.py:224-226)
   bool upper_zeroed = false;
   bool gram = false;             // built from a host-evaluated Gram matrix: no kernel, no packed inputs
   int psd_flags = 0;             // DFH_FIT_PROJECT_FIRST / DFH_FIT_TRY_BEFORE_PROJECT the fit ran under (L is not chol(K + noise I) of the kernel's K)

@@ -37,7 +37,8 @@ static int gp_alpha_and_lml(dfh_gp* gp, const double* dy, double* lml) {
   DFH_TRY(trsv_both(ctx, gp->L, n, n, gp->inv, gp->alpha, gp->refine.data()));
   double logdet = 0.0, dot = 0.0;
   DFH_TRY(logdet_and_dot(ctx, gp->L, n, n, dy, gp->alpha, &logdet, &dot));
-  if (lml) *lml = lml_value(logdet, dot, n);
+  gp->lml = lml_value(logdet, dot, n);
+  if (lml) *lml = gp->lml;
   return DFH_OK;
 }
 

@@ -836,6 +836,15 @@ class FittedGP(object):
     check(self.engine.lib.dfh_gp_refine_steps(self.handle, out))
     return list(out)
 
+  def lml_grad(self):
+    """ (grad, lml): the gradient of the log marginal likelihood in the tuner's coordinates -- [log scale,
+        log bw_0 .. log bw_{d-1}, log noise_var, constant mean] -- and the value itself (dfh_gp_lml_grad).
+        A single SE / Matern kernel (nu <= 2.5) fitted from its descriptor; anything else raises ValueError. """
+    grad = np.empty(self.d + 3, dtype=np.float64)
+    lml = C.c_double(0)
+    check(self.engine.lib.dfh_gp_lml_grad(self.handle, _ptr(grad), C.byref(lml)))
+    return grad, lml.value
+
   def get_L(self):
     return self._get(GET_L, (self.n, self.n))
 

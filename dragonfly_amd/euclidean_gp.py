@@ -8,8 +8,9 @@ fitter and stay in HBM: SURVEY.md section 8f item 1).  Stand-alone the fitter of
 reference's maximum-likelihood strategies ('rand', 'rand_exp_sampling', the tree searches) and its
 posterior sampling of the hyper-parameters ('post_sampling' with the slice sampler,
 dragonfly_amd/hp_sampling.py) -- the bandit's default criterion is 'ml-post_sampling'
-(opt/gp_bandit.py:51); only NUTS, which needs the gradient of the marginal likelihood, is left to
-dragonfly_amd.install under a real Dragonfly.
+(opt/gp_bandit.py:51).  The NUTS sampler itself is left to dragonfly_amd.install under a real Dragonfly: the
+gradient of the marginal likelihood it asks each GP for runs on the device
+(GP.compute_grad_log_marginal_likelihood, dfh_gp_lml_grad).
 """
 from argparse import Namespace
 from itertools import product as itertools_product

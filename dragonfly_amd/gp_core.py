@@ -309,6 +309,38 @@ class GP(object):
       return -0.0
     return self._need_fit().lml
 
+  def compute_grad_log_marginal_likelihood(self, param, param_num=None):
+    """ gp_core.py:229-240, in the reference's convention: 'scale', 'noise_var' and 'same_dim_bandwidths' /
+        ('dim_bandwidths', c) as its kernels' gradient methods differentiate (kernel.py:202-217, 301-322: in
+        log scale, and in the bandwidth itself), 'noise_var' in log noise_var, 'noise_mean' as sum(alpha).  One
+        device call (FittedGP.lml_grad) serves every parameter and is kept with the posterior: until
+        build_posterior, set_data or add_data_* replace it (_invalidate). """
+    if self._generic:
+      raise NotImplementedError('compute_grad_log_marginal_likelihood: this GP evaluates its kernel on the host '
+                                '(host-kernel mode); the device gradient needs a kernel with a device description.')
+    fitted = self._need_fit()
+    if fitted is None:
+      raise RuntimeError('compute_grad_log_marginal_likelihood needs training data.')
+    if 'lml_grad' not in self._cache:
+      try:
+        self._cache['lml_grad'] = fitted.lml_grad()[0]
+      except ValueError as exc:
+        raise NotImplementedError('compute_grad_log_marginal_likelihood: %s' % (exc))
+    grad = self._cache['lml_grad']
+    dim = fitted.d
+    if param == 'scale':
+      return float(grad[0])
+    if param == 'noise_var':
+      return float(grad[dim + 1])
+    if param == 'noise_mean':
+      return float(grad[dim + 2])
+    bws = np.ravel(np.asarray(self.kernel.hyperparams['dim_bandwidths'], dtype=float))
+    if param == 'same_dim_bandwidths':
+      return float(np.sum(grad[1:dim + 1]) / bws[0])
+    if param == 'dim_bandwidths':
+      return float(grad[1 + param_num] / bws[param_num])
+    raise ValueError('Unknown parameter for the gradient of the marginal likelihood: %s' % (param,))
+
   def __str__(self):
     return '%s, noise-var=%0.3f (n=%d)'%(self._child_str(), self.noise_var, len(self.Y))
 

@@ -195,8 +195,9 @@ class PosteriorHPSampler(object):
   def sample(self, num_samples):
     opts = self.f.options
     if opts.post_hp_tune_method != 'slice':
-      raise NotImplementedError('post_hp_tune_method=%s: only the slice sampler runs stand-alone (NUTS needs the '
-                                'gradient of the marginal likelihood; use dragonfly_amd.install).' % (opts.post_hp_tune_method))
+      raise NotImplementedError('post_hp_tune_method=%s: only the slice sampler runs stand-alone.  The gradient of '
+                                'the marginal likelihood exists (GP.compute_grad_log_marginal_likelihood); a NUTS sampler '
+                                'does not: use dragonfly_amd.install with a real Dragonfly.' % (opts.post_hp_tune_method))
     offset = opts.post_hp_tune_offset
     num_dscr = self.num_hps - self.num_cts
     total = (num_samples - 1) * offset + 1

@@ -288,6 +288,22 @@ int dfh_gp_lml_batch(dfh_ctx* ctx, const dfh_kernel_desc* descs, int32_t nb, con
  * [ceil(n/512)] receives the number of steps per block (0 everywhere for well-conditioned fits). */
 int dfh_gp_refine_steps(dfh_gp* gp, int32_t* steps_out);
 
+/* Gradient of the log marginal likelihood of a fit (GP.compute_grad_log_marginal_likelihood,
+ * gp/gp_core.py:229-240) in the tuner's coordinates, every component from one inverse of the
+ * factored matrix and one pass over it:
+ *   grad_out[0]        d lml / d log scale
+ *   grad_out[1 + c]    d lml / d log bw_c, c < dim
+ *   grad_out[dim + 1]  d lml / d log noise_var
+ *   grad_out[dim + 2]  d lml / d (constant mean) = sum alpha
+ * It is the gradient of the matrix as factored, K + (noise_var + the jitter the fit added) I.  A
+ * pair of points at squared distance 0 (the diagonal, duplicated rows) adds exactly 0 to every
+ * bandwidth component.  lml_out (or NULL) receives the value dfh_gp_fit reported.
+ * For a handle of dfh_gp_fit / dfh_gp_append with a single SE or MATERN kernel, nu 0.5, 1.5 or
+ * 2.5; every other kernel kind, a handle of dfh_gp_fit_gram and a fit under DFH_FIT_PROJECT_FIRST /
+ * DFH_FIT_TRY_BEFORE_PROJECT return DFH_ERR_BAD_ARG, dfh_last_error() naming the case.
+ * Deterministic: the same bits on every call.                                                   */
+int dfh_gp_lml_grad(dfh_gp* gp, double* grad_out /* [dim + 3], host */, double* lml_out /* or NULL */);
+
 /* GP.eval(X_test, 'std') without the mean function (gp_core.py:165-190):
  *   mu_out[m]  = K(Xs, X) alpha           (caller adds mean_func(Xs))
  *   sd_out[m]  = sqrt(k(x,x) - ||L \ k(X,x)||^2), no clipping -> NaN for negative variance
