@@ -96,6 +96,7 @@ SIGNATURES = {
   'dfh_gp_n': (C.c_int64, [C.c_void_p]),
   'dfh_gp_refine_steps': (C.c_int, [C.c_void_p, c_int32_p]),
   'dfh_gp_lml_grad': (C.c_int, [C.c_void_p, C.c_void_p, c_double_p]),
+  'dfh_gp_lml_grad_groups': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_double_p]),
   'dfh_gp_predict': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                C.c_void_p, C.c_void_p]),
   'dfh_gp_predict_covar': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,

@@ -845,6 +845,27 @@ class FittedGP(object):
     check(self.engine.lib.dfh_gp_lml_grad(self.handle, _ptr(grad), C.byref(lml)))
     return grad, lml.value
 
+  def lml_grad_layout(self):
+    """ [(group, column)] of the bandwidth entries of lml_grad_groups, in order: the groups' columns as the
+        descriptor lists them; group 0 and every column for a single kernel. """
+    spec = self.spec
+    if spec is None:
+      raise ValueError('lml_grad_layout: a Gram-mode fit keeps no kernel.')
+    if spec.groups is None:
+      return [(0, c) for c in range(spec.dim)]
+    return [(g, int(c)) for g, cols in enumerate(spec.groups) for c in cols]
+
+  def lml_grad_groups(self):
+    """ (grad, lml) as lml_grad, with one entry per bandwidth of every group (dfh_gp_lml_grad_groups):
+        [log scale, the log bandwidths in lml_grad_layout's order, log noise_var, constant mean].  A single SE /
+        Matern kernel, or an additive / product kernel of plain SE / Matern groups (nu <= 2.5); anything else
+        raises ValueError. """
+    nbw = self.d if self.spec is None else len(self.lml_grad_layout())
+    grad = np.empty(nbw + 3, dtype=np.float64)
+    lml = C.c_double(0)
+    check(self.engine.lib.dfh_gp_lml_grad_groups(self.handle, _ptr(grad), grad.size, C.byref(lml)))
+    return grad, lml.value
+
   def get_L(self):
     return self._get(GET_L, (self.n, self.n))
 

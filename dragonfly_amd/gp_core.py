@@ -314,13 +314,19 @@ class GP(object):
         ('dim_bandwidths', c) as its kernels' gradient methods differentiate (kernel.py:202-217, 301-322: in
         log scale, and in the bandwidth itself), 'noise_var' in log noise_var, 'noise_mean' as sum(alpha).  One
         device call (FittedGP.lml_grad) serves every parameter and is kept with the posterior: until
-        build_posterior, set_data or add_data_* replace it (_invalidate). """
+        build_posterior, set_data or add_data_* replace it (_invalidate).
+        An AdditiveKernel or CoordinateProductKernel of SE / Matern kernels (the reference has no gradient of either)
+        serves the same names from FittedGP.lml_grad_groups: ('dim_bandwidths', c) is the bandwidth of column c of the
+        input space, wherever the groupings put it; 'same_dim_bandwidths' sums over every bandwidth. """
     if self._generic:
       raise NotImplementedError('compute_grad_log_marginal_likelihood: this GP evaluates its kernel on the host '
                                 '(host-kernel mode); the device gradient needs a kernel with a device description.')
     fitted = self._need_fit()
     if fitted is None:
       raise RuntimeError('compute_grad_log_marginal_likelihood needs training data.')
+    spec = getattr(fitted, 'spec', None)
+    if spec is not None and spec.kind in ('additive', 'product'):
+      return self._grouped_grad_log_marginal_likelihood(fitted, param, param_num)
     if 'lml_grad' not in self._cache:
       try:
         self._cache['lml_grad'] = fitted.lml_grad()[0]
@@ -339,6 +345,33 @@ class GP(object):
       return float(np.sum(grad[1:dim + 1]) / bws[0])
     if param == 'dim_bandwidths':
       return float(grad[1 + param_num] / bws[param_num])
+    raise ValueError('Unknown parameter for the gradient of the marginal likelihood: %s' % (param,))
+
+  def _grouped_grad_log_marginal_likelihood(self, fitted, param, param_num):
+    """ the same for an additive / product kernel: one FittedGP.lml_grad_groups call per posterior """
+    if 'lml_grad_groups' not in self._cache:
+      try:
+        grad = fitted.lml_grad_groups()[0]
+      except ValueError as exc:
+        raise NotImplementedError('compute_grad_log_marginal_likelihood: %s' % (exc))
+      columns = [c for _, c in fitted.lml_grad_layout()]
+      bws = np.concatenate([np.ravel(np.asarray(b, dtype=float)) for b in fitted.spec.sub_bandwidths])
+      self._cache['lml_grad_groups'] = (grad, columns, bws)
+    grad, columns, bws = self._cache['lml_grad_groups']
+    nbw = len(columns)
+    if param == 'scale':
+      return float(grad[0])
+    if param == 'noise_var':
+      return float(grad[nbw + 1])
+    if param == 'noise_mean':
+      return float(grad[nbw + 2])
+    if param == 'same_dim_bandwidths':
+      return float(np.sum(grad[1:nbw + 1]) / bws[0])
+    if param == 'dim_bandwidths':
+      if param_num not in columns:
+        raise ValueError('No group of the kernel holds column %s.' % (param_num,))
+      q = columns.index(param_num)
+      return float(grad[1 + q] / bws[q])
     raise ValueError('Unknown parameter for the gradient of the marginal likelihood: %s' % (param,))
 
   def __str__(self):

@@ -123,6 +123,17 @@ class EuclideanMFGP(MFGP):
     self._test_fidel_domain_dims(len(ZZ[0]), len(XX[0]))
     return list(np.hstack((np.asarray(ZZ), np.asarray(XX))))
 
+  def compute_grad_log_marginal_likelihood(self, param, param_num=None):
+    """ GP.compute_grad_log_marginal_likelihood with two names of this class's own (the reference has no gradient of a
+        product kernel): ('fidel_dim_bandwidths', c) and ('domain_dim_bandwidths', c), the bandwidth of column c of the
+        fidelity space / of the domain.  SE / Matern fidelity and domain kernels; an additive domain model is a nested
+        factor of the product, which the device does not differentiate (NotImplementedError). """
+    if param == 'fidel_dim_bandwidths':
+      param, param_num = 'dim_bandwidths', self.fidel_coords[param_num]
+    elif param == 'domain_dim_bandwidths':
+      param, param_num = 'dim_bandwidths', self.domain_coords[param_num]
+    return super(EuclideanMFGP, self).compute_grad_log_marginal_likelihood(param, param_num)
+
   def _training_rows(self, rows, data_idxs):
     return list(rows[:self.num_tr_data]) if data_idxs is None else [rows[i] for i in data_idxs]
 

@@ -304,6 +304,30 @@ int dfh_gp_refine_steps(dfh_gp* gp, int32_t* steps_out);
  * Deterministic: the same bits on every call.                                                   */
 int dfh_gp_lml_grad(dfh_gp* gp, double* grad_out /* [dim + 3], host */, double* lml_out /* or NULL */);
 
+/* The same gradient with one entry per bandwidth of every group, so that additive and product
+ * kernels have one too (the reference's AdditiveKernel / CoordinateProductKernel have no gradient).
+ * Q = dim for a single SE / MATERN kernel; Q = group_off[n_groups] for ADDITIVE / PRODUCT.
+ *   grad_out[0]       d lml / d log scale            (the outer scale)
+ *   grad_out[1 + q]   d lml / d log bandwidth q      (q < Q: position in the flattened sub_bw /
+ *                                                    group_dims arrays; for a single kernel, column q)
+ *   grad_out[Q + 1]   d lml / d log noise_var
+ *   grad_out[Q + 2]   d lml / d (constant mean) = sum alpha
+ * sub_scale[g] enters the value and is not differentiated (the fitters hold it at 1).
+ * With S_c = ((x_ic - x_jc) / bw_c)^2 for a column c of group g and dsq_g the group's squared scaled
+ * distance, dK / d log bw_c = scale * s_g k_g'(dsq_g) * (-2 S_c) for an ADDITIVE kernel and
+ * scale * (prod_{h != g} s_h k_h) * s_g k_g'(dsq_g) * (-2 S_c) for a PRODUCT; a pair of points at
+ * squared distance 0 IN GROUP g's COLUMNS adds exactly 0 to group g's bandwidths.
+ * For a handle of dfh_gp_fit / dfh_gp_append whose kernel is a single SE / MATERN kernel, or an
+ * ADDITIVE or PRODUCT kernel whose groups are all SE / MATERN, nu 0.5, 1.5 or 2.5 throughout.
+ * DFH_ERR_BAD_ARG, dfh_last_error() naming the case: a handle of dfh_gp_fit_gram; a fit under
+ * DFH_FIT_PROJECT_FIRST / DFH_FIT_TRY_BEFORE_PROJECT; a POLY / EXPDECAY / HAMMING kernel or part; an
+ * ESP kernel; a nested factor (group_factor != NULL); len other than Q + 3.
+ * For a single kernel the result is dfh_gp_lml_grad's, bit for bit.  The device workspace is that
+ * of dfh_gp_lml_grad plus n doubles per group: one pass over the matrix per group.
+ * Deterministic: the same bits on every call.                                                   */
+int dfh_gp_lml_grad_groups(dfh_gp* gp, double* grad_out /* [len], host */, int64_t len /* must be Q + 3 */,
+                           double* lml_out /* or NULL */);
+
 /* GP.eval(X_test, 'std') without the mean function (gp_core.py:165-190):
  *   mu_out[m]  = K(Xs, X) alpha           (caller adds mean_func(Xs))
  *   sd_out[m]  = sqrt(k(x,x) - ||L \ k(X,x)||^2), no clipping -> NaN for negative variance
